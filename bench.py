@@ -9,11 +9,17 @@ instances (variance kernel -> tightening + SQP-GN/IPM kernel) followed by the sy
 plant kernel that produces the next observation.  Inputs are resident in HBM; the GP,
 hyperparameters, initial states and reference are synthetic and seeded
 (gpmpc/synthetic.py).  N>1: one process per GPU (torch.distributed, RCCL), instances
-sharded by rank, no collective in the data path; barrier + max-over-ranks timing.  With N>1 and
-the default partition the line also carries ``weak_per_gpu``: the same step with 1024 instances on
-every GPU (a second timed run, after the strong one).
+sharded by rank, no collective in the data path; barrier + max-over-ranks timing.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds the
+secondary measurements, each a run of its own after the timed steps: ``cpu_baseline`` (the C++ CPU
+restatement on the same window), ``single_instance_gpu`` (the B=1 drop-in call) and, with N>1 and
+the default partition, ``weak_per_gpu``: the same step with 1024 instances on every GPU.  Without
+``--full`` these fields are null.  ``--dump-outputs DIR`` writes the arrays the last timed step
+returned as ``DIR/<name>.npy`` (float64; the inputs are seeded, so two builds can be compared
+output for output).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 ``--gpus N`` without torchrun launches the N ranks itself (gpmpc/launch.py, before any GPU
@@ -201,6 +207,27 @@ def single_instance_gpu(spec, gps, H, lqr_mats, x0, phase, warmup, steps, dev, q
                       f"timed with perf_counter after {warmup} untimed; host_ms = wall - kernel events"}
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: all files together stay below this
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``arrays`` (name -> array with one leading row per instance, in global instance
+    order) as ``out_dir/<name>.npy`` in float64.  When they exceed DUMP_LIMIT_BYTES together, the
+    same seeded sample of the instances is kept in every array and its ids go to ``instance.npy``."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // max(n, 1) for a in arrays.values()) + 8   # + the id of a sampled row
+    budget = DUMP_LIMIT_BYTES - 1024 * (len(arrays) + 1)                     # .npy headers
+    if n * row_bytes > budget:
+        keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, budget // row_bytes, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["instance"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _build_info():
     """Provenance of the library this run loaded (gpmpc_build_id against the tree's source hash)."""
     from gpmpc import _lib
@@ -264,6 +291,14 @@ def parse_args(argv=None):
                          "tools/shard_sweep.sh); value then counts this shard's instances")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal: host sleep instead of the GPU step (launcher / shards / timing)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements: the CPU baseline "
+                         "(cpu_baseline), the B=1 drop-in timing (single_instance_gpu) and, with N>1 GPUs and the "
+                         "default partition, the weak-scaled run (weak_per_gpu); a plain run reports them as null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (u0, the planned "
+                         "trajectory, the solver status and residuals, the next observation) as DIR/<name>.npy "
+                         f"in float64; above {DUMP_LIMIT_BYTES // 10**6} MB a fixed, seeded sample of the instances")
     return ap.parse_args(argv)
 
 
@@ -410,10 +445,10 @@ def run_gpu(args, rank, local_rank, world, weak_secondary=False):
         fitc = GPMPC.precompute_sparse_posterior_mean(me, min(args.fitc, N))
     traj = spec.reference_trajectory()
 
-    def measure(ids, total_instances):
+    def measure(ids, total_instances, dump=False):
         """One timed closed-loop run of this rank's instances ``ids`` (global ids of a
         ``total_instances`` job): W untimed steps, barrier + synchronize, K timed steps, barrier +
-        synchronize, max over ranks."""
+        synchronize, max over ranks.  ``dump``: also return the last step's outputs (--dump-outputs)."""
         B = len(ids)
         solver = BatchSolver(spec, H, B, device=dev, qp_tol=args.qp_tol, qp_mu0=args.qp_mu0)
         if args.seg is not None:
@@ -474,7 +509,15 @@ def run_gpu(args, rank, local_rank, world, weak_secondary=False):
         # instance-steps the statistics cover: every rank's (all-reduced) or, for an emulated shard
         # (no process group), this shard's own
         n_is = (B if emulated else total_instances) * args.steps
-        return {"B": B, "solver": solver, "elapsed": elapsed, "launch": solver.launch_info(), "t_enqueue": t_enqueue, "sqp_list": sqp_list,
+        outputs = None
+        if dump:   # what the last timed step handed back, read after the clock has stopped
+            xs, us, _ = solver.solution()
+            outputs = {"u0": solver.u0, "x_plan": xs, "u_plan": us, "status": solver.status,
+                       "sqp_iter": solver.sqp_iter, "qp_iter": solver.qp_iter, "residuals": solver.res,
+                       "next_obs": obs}
+            outputs = {k: v.cpu().numpy() for k, v in outputs.items()}
+        return {"B": B, "outputs": outputs,
+                "solver": solver, "elapsed": elapsed, "launch": solver.launch_info(), "t_enqueue": t_enqueue, "sqp_list": sqp_list,
                 "var_list": var_list, "sqp_sum": sqp_sum, "var_sum": var_sum, "x0_all": x0_all,
                 "phase_all": phase_all, "value": total_instances * args.steps / elapsed,
                 "sqp_mean": float(sums[0]) / n_is, "lin_mean": float(sums[2]) / n_is, "qp_mean": float(sums[1]) / n_is,
@@ -486,9 +529,16 @@ def run_gpu(args, rank, local_rank, world, weak_secondary=False):
     # weak: rank*B .. rank*B+B-1), no collective in the data path
     ids = D.shard_slice(args.global_batch, rank, world) if args.global_batch else D.shard_range(args.batch, rank)
     total_instances = args.global_batch or args.batch * world
-    m = measure(ids, total_instances)
+    m = measure(ids, total_instances, dump=bool(args.dump_outputs))
     if emulated:   # this shard's own throughput (the job's is the slowest shard's time over all of them)
         m["value"] = len(ids) * args.steps / m["elapsed"]
+    if args.dump_outputs:
+        parts = [m["outputs"]]
+        if dist is not None:   # the ranks' contiguous slices, in rank order, are the global instance order
+            parts = [None] * world
+            dist.all_gather_object(parts, m["outputs"])
+        if rank == 0 or emulated:
+            dump_outputs(args.dump_outputs, {k: np.concatenate([p[k] for p in parts]) for k in parts[0]})
     weak = None
     if weak_secondary and world > 1 and not emulated:
         w = measure(D.shard_range(WEAK_BATCH, rank), WEAK_BATCH * world)
@@ -540,12 +590,12 @@ def run_gpu(args, rank, local_rank, world, weak_secondary=False):
         except (OSError, ValueError, KeyError):
             traffic = None
         single = None
-        if world == 1 and not emulated and not args.no_single_instance and not args.fitc:
+        if args.full and world == 1 and not emulated and not args.no_single_instance and not args.fitc:
             single = single_instance_gpu(spec, gps, H, lqr_mats, m["x0_all"][ids.start], m["phase_all"][ids.start],
                                          args.warmup, args.steps, dev, qp_tol=args.qp_tol, qp_mu0=args.qp_mu0,
                                          variance=args.variance)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and not emulated:   # rank 0 at N=1 only
+        if args.full and world == 1 and not args.no_cpu_baseline and not emulated:   # rank 0 at N=1 only
             cpu = cpu_baseline(spec, data, hyp, H, args.cpu_seconds, lqr_mats, m["x0_all"], m["phase_all"], list(ids),
                                args.warmup, args.steps, fitc=fitc, love_roots=solver.love_roots, qp_tol=args.qp_tol)
         sq = np.array(sqp_list) if sqp_list else np.zeros(1)
@@ -654,7 +704,9 @@ def main(argv=None):
         args.gpus = world
     elif world != args.gpus:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}; using WORLD_SIZE", file=sys.stderr)
-    weak_secondary = resolve_partition(args)
+    if args.dry_run and args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the GPU step's outputs: not available with --dry-run")
+    weak_secondary = resolve_partition(args) and args.full   # the second timed run belongs to --full
     if args.dry_run:
         run_dry(args, rank, world, weak_secondary)
     else:

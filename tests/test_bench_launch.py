@@ -57,9 +57,9 @@ def test_global_batch_strong_scaling_slices():
 
 def test_default_partition_is_the_metrics_global_batch():
     """Without --batch, --gpus N splits the metric's global batch 1024 over the N ranks (strong
-    scaling: the driver's SCALE runs measure "batch 1024 @1/2/4/8 GPU"), and the line carries the
-    weak per-GPU figure (1024 instances on every GPU) as a secondary field."""
-    out = _run(["--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "0"])
+    scaling: the driver's SCALE runs measure "batch 1024 @1/2/4/8 GPU"), and with --full the line
+    carries the weak per-GPU figure (1024 instances on every GPU) as a secondary field."""
+    out = _run(["--gpus", "2", "--dry-run", "--full", "--steps", "3", "--warmup", "0"])
     assert out["scaling"] == "strong" and out["config"]["global_batch"] == 1024
     assert out["config"]["batch_per_gpu"] == 512
     assert [s[:2] for s in out["shards"]] == [[0, 512], [512, 1024]]
@@ -67,6 +67,8 @@ def test_default_partition_is_the_metrics_global_batch():
     assert w["scaling"] == "weak" and w["batch_per_gpu"] == 1024
     assert [s[:2] for s in w["shards"]] == [[0, 1024], [1024, 2048]]
     assert abs(w["value"] - 2048 * 3 / (w["ms_per_step"] * 3e-3)) <= 1e-6 * w["value"]
+    plain = _run(["--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "0"])   # no second run without --full
+    assert plain["weak_per_gpu"] is None and plain["config"]["batch_per_gpu"] == 512
     one = _run(["--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "0"])
     assert one["scaling"] == "strong" and one["config"]["global_batch"] == 1024 and one["weak_per_gpu"] is None
     assert one["shards"][0][:2] == [0, 1024]
@@ -96,7 +98,8 @@ def test_bench_line_contract_on_the_gpu():
     """The driver's bench line on a short run: the contract keys, the roofline and
     cpu_baseline objects, the per-step kernel times and solver statistics are present and
     consistent (value = instances x steps / time, every instance-step converged)."""
-    out = _gpu_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64", "--cpu-seconds", "1"])
+    out = _gpu_bench(["--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--batch", "64",
+                      "--cpu-seconds", "1"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in out, k
@@ -117,6 +120,68 @@ def test_bench_line_contract_on_the_gpu():
     cb = out["cpu_baseline"]
     assert cb["value"] > 0 and cb["cores"] >= 1 and cb["kind"] in ("port", "reference")
     assert cb["window"] == [1, 4] and cb["sqp_iter_mean"] > 0   # the GPU leg's own timed window
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run (no --full) times its steps only: the secondary measurements are null, the
+    headline keys keep their meaning.  --dump-outputs writes the last timed step's arrays in float64,
+    one row per instance, and a second run with the same arguments writes the same numbers."""
+    import numpy as np
+
+    B, H, nx, nu = 16, 30, 6, 2
+    dumps = []
+    for name in ("a", "b"):
+        out = _gpu_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", str(B),
+                          "--dump-outputs", str(tmp_path / name)])
+        assert out["cpu_baseline"] is None and out["single_instance_gpu"] is None and out["weak_per_gpu"] is None
+        assert out["steps"] == 2 and out["dtype"] == "f64" and out["higher_is_better"] is True
+        assert abs(out["value"] - B * 2 / (out["ms_per_step"] * 2e-3)) <= 1e-6 * out["value"]
+        assert out["status_counts"]["0"] == B * 2
+        dumps.append({f.stem: np.load(f) for f in sorted((tmp_path / name).glob("*.npy"))})
+    shapes = {"u0": (B, nu), "x_plan": (B, H + 1, nx), "u_plan": (B, H, nu), "status": (B,), "sqp_iter": (B,),
+              "qp_iter": (B,), "residuals": (B, 4), "next_obs": (B, nx)}
+    assert {k: v.shape for k, v in dumps[0].items()} == shapes
+    for k, a in dumps[0].items():
+        assert a.dtype == np.float64 and np.isfinite(a).all(), k
+        np.testing.assert_array_equal(a, dumps[1][k], err_msg=k)
+    a = dumps[0]
+    assert (a["status"] == 0).all() and (a["sqp_iter"] >= 1).all()
+    # the step's outputs hang together: u0 is the plan's first input, and differs between instances
+    np.testing.assert_array_equal(a["u0"], a["u_plan"][:, 0])
+    assert np.ptp(a["u0"], axis=0).max() > 0
+
+
+def test_dump_outputs_sample_is_seeded_and_within_the_limit(tmp_path, monkeypatch):
+    """dump_outputs writes float64 whatever it is given; above the size limit every array keeps the
+    same seeded sample of instances (ids in instance.npy), and the files stay below the limit."""
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    sys.path.insert(0, str(ROOT / "gp-mpc_amd"))
+    import bench
+
+    n = 1000
+    arrays = {"u0": np.arange(2 * n, dtype=np.float64).reshape(n, 2), "status": np.arange(n, dtype=np.int32),
+              "x_plan": np.arange(n * 3 * 4, dtype=np.float64).reshape(n, 3, 4)}
+    bench.dump_outputs(tmp_path / "all", arrays)
+    got = {f.stem: np.load(f) for f in (tmp_path / "all").glob("*.npy")}
+    assert set(got) == set(arrays) and all(g.dtype == np.float64 for g in got.values())
+    for k in arrays:
+        np.testing.assert_array_equal(got[k], arrays[k])
+    assert bench.DUMP_LIMIT_BYTES <= 64 * 10**6
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40_000)   # the arrays hold 124 kB
+    for name in ("s1", "s2"):
+        bench.dump_outputs(tmp_path / name, arrays)
+    s1 = {f.stem: np.load(f) for f in (tmp_path / "s1").glob("*.npy")}
+    s2 = {f.stem: np.load(f) for f in (tmp_path / "s2").glob("*.npy")}
+    assert set(s1) == set(arrays) | {"instance"}
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").glob("*.npy")) <= 40_000
+    ids = s1["instance"].astype(int)
+    assert 200 < len(ids) < n and (np.diff(ids) > 0).all()
+    for k in arrays:
+        np.testing.assert_array_equal(s1[k], arrays[k][ids])
+        np.testing.assert_array_equal(s1[k], s2[k])
 
 
 def test_flop_counts_match_survey_8d():

@@ -1,15 +1,17 @@
 """Every reference citation (``gpmpc/<file>.py:N``, ``scripts/run_gp_mpc.py:N``, ...) in the
 boundary header, the package, the oracle, the tests and the docs points at lines that exist in
-/root/reference, and the key boundary citations point at the symbol they name.  Skipped when the
-reference tree is absent (the GPU box)."""
+the reference, and the key boundary citations point at the symbol they name.  The reference is
+not read here: tests/golden/reference_index.json records, for each cited file, its number of lines
+and the lines that hold each marker text of KEY (tests/golden/make_citation_index.py)."""
 
+import json
 import re
 from pathlib import Path
 
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
-REF = Path("/root/reference")
+INDEX = ROOT / "tests" / "golden" / "reference_index.json"
 FILES = {"gp.py": "gpmpc/gp.py", "mpc.py": "gpmpc/mpc.py", "gpmpc.py": "gpmpc/gpmpc.py",
          "plotting.py": "gpmpc/plotting.py", "run_gp_mpc.py": "scripts/run_gp_mpc.py",
          "gp_mpc_config.yaml": "scripts/gp_mpc_config.yaml", "pyproject.toml": "pyproject.toml",
@@ -19,11 +21,12 @@ PAT = re.compile(r"\b(gp|mpc|gpmpc|plotting|run_gp_mpc)\.py:(\d+(?:-\d+)?(?:,\d+
 SOURCES = ["include", "gp-mpc_amd", "oracle", "tests", "tools", "bench.py", "__graft_entry__.py", "DESIGN.md",
            "INTEGRATION.md", "README.md", "BASELINE.md"]
 
-pytestmark = pytest.mark.skipif(not REF.is_dir(), reason="reference tree not present")
 
-
-def _ref_lines(name):
-    return (REF / FILES[name]).read_text().splitlines()
+@pytest.fixture(scope="module")
+def index():
+    idx = json.loads(INDEX.read_text())
+    assert {n: e["path"] for n, e in idx.items()} == FILES
+    return idx
 
 
 def _citations():
@@ -47,12 +50,12 @@ def _citations():
                         yield f"{f.relative_to(ROOT)}:{ln}", name, int(lo), int(hi or lo)
 
 
-def test_every_citation_is_in_range():
+def test_every_citation_is_in_range(index):
     bad = []
     n = 0
     for where, name, lo, hi in _citations():
         n += 1
-        nl = len(_ref_lines(name))
+        nl = index[name]["lines"]
         if not (1 <= lo <= hi <= nl):
             bad.append(f"{where}: {name}:{lo}-{hi} (file has {nl} lines)")
     assert n > 100, n
@@ -89,8 +92,9 @@ KEY = [
 
 
 @pytest.mark.parametrize("src,name,rng,text", KEY)
-def test_key_citation_points_at_its_symbol(src, name, rng, text):
+def test_key_citation_points_at_its_symbol(index, src, name, rng, text):
     cites = {(n, lo, hi) for where, n, lo, hi in _citations() if where.rsplit(":", 1)[0] == src}
     assert (name, *rng) in cites, f"{src} does not cite {name}:{rng[0]}-{rng[1]}"
-    lines = _ref_lines(name)[rng[0] - 1:rng[1]]
-    assert any(text in ln for ln in lines), f"{name}:{rng[0]}-{rng[1]} does not contain {text!r}"
+    assert 1 <= rng[0] <= rng[1] <= index[name]["lines"]
+    hits = index[name]["markers"][text]   # the reference lines that contain the marker
+    assert any(rng[0] <= ln <= rng[1] for ln in hits), f"{name}:{rng[0]}-{rng[1]} does not contain {text!r}"

@@ -2,7 +2,7 @@
 # Profile of the driver's own bench command (python3 bench.py --gpus 1 --steps 20 --warmup 5)
 # on one MI355X, run through gpurun from the repo root:
 #   bash tools/driver_prof.sh OUTDIR [extra bench args...]
-# 1. the bench line itself (untraced)
+# 1. the bench line itself (untraced, --full: with the CPU baseline and the B=1 drop-in)
 # 2. rocprofv3 --kernel-trace --stats of the same command (per-dispatch durations)
 # 3. one SQ PMC pass (wave cycles, wait/active split, VALU/MFMA issue) of the same command
 # 4. FETCH_SIZE and WRITE_SIZE passes (each its own run) -> tools/pmc_summary.py
@@ -13,7 +13,7 @@ shift
 ARGS="--gpus 1 --steps 20 --warmup 5"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
-timeout -k 10 300 python3 -u bench.py $ARGS "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python3 -u bench.py $ARGS --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
     python3 bench.py $ARGS --no-cpu-baseline "$@" > "$OUT/trace.log" 2>&1
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
