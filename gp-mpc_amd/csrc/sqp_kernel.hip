@@ -33,6 +33,12 @@
 #ifndef GPMPC_SOLVE_STAMP    // 1: per-instance solve time in stats slots 10-11 (A/B variants: 0)
 #define GPMPC_SOLVE_STAMP 1
 #endif
+#ifndef GPMPC_TIGHTEN_LDS   // 1: tightening gain table staged in LDS, variables split over the half-waves (A/B variants: 0)
+#define GPMPC_TIGHTEN_LDS 1
+#endif
+#ifndef GPMPC_LIN_EARLY   // 1: cached linearisation rows loaded before the tightening arithmetic (A/B variants: 0)
+#define GPMPC_LIN_EARLY 1
+#endif
 #ifndef GPMPC_PHASE_LANE   // (round-6 A/B of phase_lane: 0 off, 1 one-wave and quad3d kernels, 2 every kernel)
 #define GPMPC_PHASE_LANE 1
 #endif
@@ -3078,10 +3084,163 @@ struct SqpKernel {
         }
 
         TPHASE(0);
+        // ---------------- stage-0 state rows (gpmpc.py:288,296,309-310; mpc.py:141,145,157-158)
+        // x_0 is pinned to obs (lbx = ubx = obs, gpmpc.py:339-340), so these rows only decide
+        // feasibility: an obs outside the stage-0 box by more than the inequality tolerance makes
+        // every QP infeasible, which acados reports as a QP failure (status 4; the reference then
+        // asserts, gpmpc.py:365).  Within the tolerance the rows enter the NLP residual only.
+        double v0 = 0.0;   // largest stage-0 state-row violation of x0 (NaN-propagating)
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            const double e = fmax(P.x_lo[i] - P.uh - x0[i], x0[i] - P.x_hi[i] - P.uh);
+            v0 = (e == e && v0 == v0) ? fmax(v0, e) : __builtin_nan("");
+        }
+        const bool x0_ok = v0 <= P.tol_ineq;   // uniform: x0 and the bounds are the same on every lane
+        // linearisation cache: the rows of the stored iterate's linearisation (StateDev::lin) are
+        // valid when the step that stored the iterate also stored them and no host call since has
+        // changed the iterate, the GPs or the model (lin_tag == lin_gen)
+        double* lin_b = S.lin ? S.lin + (size_t)b * H * NX * GS : nullptr;
+        const bool lin_hit = lin_b != nullptr && P.lin_gen != 0 &&
+                             __builtin_amdgcn_readfirstlane(S.lin_tag[b]) == P.lin_gen;
+        // GPMPC_LIN_EARLY: the cached rows of the first SQP iteration are loaded here, into registers,
+        // and go to G' after the tightening, so their round trip runs under its arithmetic (split
+        // kernels: H <= 31 bounds the rows per lane)
+        constexpr bool kLinEarly = GPMPC_LIN_EARLY && SPL && kMfma;
+        constexpr int kLinRegs = kLinEarly ? (31 * NX * GS + 63) / 64 : 1;
+        double lin_r[kLinRegs], lin_F[NX];
+        const bool lin_early = kLinEarly && lin_hit && x0_ok;
+        auto lin_issue = [&]() {
+            if constexpr (kLinEarly) {
+                if (lin_early) {
+#pragma unroll
+                    for (int j = 0; j < kLinRegs; ++j) {
+                        const int e = lane + 64 * j;
+                        lin_r[j] = lin_b[e < H * NX * GS ? e : 0];
+                    }
+#pragma unroll
+                    for (int i = 0; i < NX; ++i) lin_F[i] = (lane < H) ? lin_b[(size_t)lane * NX * GS + i * GS + NB] : 0.0;
+                }
+            }
+        };
         // ---------------- constraint tightening from the previous solution (gpmpc.py:425-498)
         double tsd[NB];  // icdf * sqrt(variance) per stage variable
 #pragma unroll
         for (int v = 0; v < NB; ++v) tsd[v] = 0.0;
+        // GPMPC_TIGHTEN_LDS: the gain table (the same for every lane, instance and step) is staged in
+        // LDS once per step by the whole wave, in the P' region (dead until the first QP; the GP
+        // scratch of the first linearisation overwrites it), and every term reads its row as a
+        // wave-uniform broadcast.  In the split kernels (H + 1 <= 32) lane k takes variables
+        // 0 .. NV - 1 of stage k and lane k + 32 the rest, in the same term order, so every sum keeps
+        // its order of additions and the tightening its bits.  Models whose table does not fit the
+        // P' region (quad3d) keep the loop below.
+        constexpr bool kTabLds = GPMPC_TIGHTEN_LDS && kMfma && NB * NUNC <= PPB;
+        if constexpr (kTabLds) {
+            if (P.tighten && S.has_prev[b]) {
+                constexpr int NG = NB * NUNC, CH = 12;
+                // (16-byte aligned rows for the wide LDS reads: the P' region starts at any double)
+                double* tab = L.P + ((L.P - smem) & 1);
+                const int n = H * NG;
+                double tr[CH];
+#pragma unroll
+                for (int j = 0; j < CH; ++j) {
+                    const int e = lane + 64 * j;
+                    tr[j] = P.tgain[e < n ? e : 0];
+                }
+                if (lane < H) {
+                    double Wt[NUNC][NGP];
+                    M::var_weights(w, w + NX, Wt);
+                    const double dt2 = P.dt * P.dt;
+#pragma unroll
+                    for (int j = 0; j < NUNC; ++j) {
+                        double acc = 0.0;
+#pragma unroll
+                        for (int g = 0; g < NGP; ++g)
+                            acc = fma(Wt[j][g], S.var[((size_t)b * H + lane) * NGP + g] + P.gp[g].sn2, acc);
+                        L.cd[lane * NUNC + j] = acc * dt2;
+                    }
+                }
+                lin_issue();
+#pragma unroll
+                for (int j = 0; j < CH; ++j) {
+                    const int e = lane + 64 * j;
+                    if (e < n) tab[e] = tr[j];
+                }
+                for (int e0 = 64 * CH; e0 < n; e0 += 64 * CH) {   // (H > 31: the rest of the table)
+#pragma unroll
+                    for (int j = 0; j < CH; ++j) {
+                        const int e = e0 + lane + 64 * j;
+                        tr[j] = P.tgain[e < n ? e : 0];
+                    }
+#pragma unroll
+                    for (int j = 0; j < CH; ++j) {
+                        const int e = e0 + lane + 64 * j;
+                        if (e < n) tab[e] = tr[j];
+                    }
+                }
+                WSYNC();
+                // diag Sigma_k = sum_{m<k} sum_q tgain[m][.][q] cd_{k-1-m}[q] (see the loop below): this
+                // lane's variables vb .. vb + NV - 1 of stage kq
+                constexpr bool kAl = (NG % 2 == 0) && ((NV * NUNC) % 2 == 0);
+                const double* trow = tab + vb * NUNC;
+                if constexpr (kAl) trow = static_cast<const double*>(__builtin_assume_aligned(trow, 16));
+                double sv[NV];
+#pragma unroll
+                for (int j = 0; j < NV; ++j) sv[j] = 0.0;
+                // a term's operands (its table row and cd of stage kq - 1 - m) are read one term ahead,
+                // every read of a term issued together; the reads are unconditional (row clamped to
+                // H - 1, unmasked cd address) so the two register sets alternate without copies
+                struct Term { double g[NV * NUNC], cd[NUNC]; bool act; };
+                auto load_t = [&](int m, Term& t) {
+                    t.act = m < kq && on_q;
+                    const double* cdk = L.cd + (t.act ? (kq - 1 - m) * NUNC : 0);   // unmasked read, value masked in term()
+                    const double* row = trow + (size_t)min(m, H - 1) * NG;
+#pragma unroll
+                    for (int q = 0; q < NUNC; ++q) t.cd[q] = cdk[q];
+                    // (odd NB: the upper half's last slot reads on into the next row, unused)
+#pragma unroll
+                    for (int e = 0; e < NV * NUNC; ++e) t.g[e] = row[e];
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                auto term = [&](const Term& t) {
+                    double cdv[NUNC];
+#pragma unroll
+                    for (int q = 0; q < NUNC; ++q) cdv[q] = t.act ? t.cd[q] : 0.0;
+#pragma unroll
+                    for (int j = 0; j < NV; ++j)
+#pragma unroll
+                        for (int q = 0; q < NUNC; ++q) sv[j] = fma(t.g[j * NUNC + q], cdv[q], sv[j]);
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                Term t0, t1;
+                load_t(0, t0);
+                int m = 0;
+                for (; m + 1 < H; m += 2) {
+                    load_t(m + 1, t1);
+                    term(t0);
+                    load_t(m + 2, t0);
+                    term(t1);
+                }
+                if (m < H) term(t0);
+                double ts[NV];
+#pragma unroll
+                for (int j = 0; j < NV; ++j) ts[j] = on_q ? P.icdf * sqrt(fmax(sv[j], 0.0)) : 0.0;
+#pragma unroll
+                for (int v = 0; v < NB; ++v) {
+                    if constexpr (SPL) {
+                        if (v < NV) tsd[v] = hi_half ? 0.0 : ts[v];
+                        else {
+                            const double up = xor32_d(ts[v - NV]);   // lane k + 32's variable v
+                            tsd[v] = hi_half ? 0.0 : up;
+                        }
+                    } else {
+                        tsd[v] = ts[v];
+                    }
+                }
+            } else {
+                lin_issue();
+            }
+        } else {
+        lin_issue();
         if (P.tighten && S.has_prev[b]) {
             if (lane < H) {
                 double Wt[NUNC][NGP];
@@ -3140,6 +3299,16 @@ struct SqpKernel {
 #pragma unroll
             for (int v = 0; v < NB; ++v) tsd[v] = on ? P.icdf * sqrt(fmax(sv[v], 0.0)) : 0.0;
         }
+        }
+        if constexpr (kLinEarly) {
+            if (lin_early) {
+#pragma unroll
+                for (int j = 0; j < kLinRegs; ++j) {
+                    const int e = lane + 64 * j;
+                    if (e < H * NX * GS) L.G[e] = lin_r[j];
+                }
+            }
+        }
         if (S.tight != nullptr && on) {
 #pragma unroll
             for (int v = 0; v < NB; ++v) S.tight[((size_t)b * (H + 1) + k) * NB + v] = tsd[v];
@@ -3148,24 +3317,6 @@ struct SqpKernel {
         auto lbv = [&](int v) { return (v < NX ? P.x_lo[v] : P.u_lo[v - NX]) + tsd[v] - P.uh; };
         auto ubv = [&](int v) { return (v < NX ? P.x_hi[v] : P.u_hi[v - NX]) - tsd[v] + P.uh; };
 
-        // ---------------- stage-0 state rows (gpmpc.py:288,296,309-310; mpc.py:141,145,157-158)
-        // x_0 is pinned to obs (lbx = ubx = obs, gpmpc.py:339-340), so these rows only decide
-        // feasibility: an obs outside the stage-0 box by more than the inequality tolerance makes
-        // every QP infeasible, which acados reports as a QP failure (status 4; the reference then
-        // asserts, gpmpc.py:365).  Within the tolerance the rows enter the NLP residual only.
-        double v0 = 0.0;   // largest stage-0 state-row violation of x0 (NaN-propagating)
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            const double e = fmax(P.x_lo[i] - P.uh - x0[i], x0[i] - P.x_hi[i] - P.uh);
-            v0 = (e == e && v0 == v0) ? fmax(v0, e) : __builtin_nan("");
-        }
-        const bool x0_ok = v0 <= P.tol_ineq;   // uniform: x0 and the bounds are the same on every lane
-        // linearisation cache: the rows of the stored iterate's linearisation (StateDev::lin) are
-        // valid when the step that stored the iterate also stored them and no host call since has
-        // changed the iterate, the GPs or the model (lin_tag == lin_gen)
-        double* lin_b = S.lin ? S.lin + (size_t)b * H * NX * GS : nullptr;
-        const bool lin_hit = lin_b != nullptr && P.lin_gen != 0 &&
-                             __builtin_amdgcn_readfirstlane(S.lin_tag[b]) == P.lin_gen;
         // store this step's final linearisation (and F of this lane's stage) before a good exit
         // (F goes into the c column of G' first, dead at this point, so the rows leave in one
         // coalesced pass)
@@ -3199,7 +3350,11 @@ struct SqpKernel {
 #else
             unsigned long long* tgp = nullptr;
 #endif
-            if (it == 0 && lin_hit) {
+            if (kLinEarly && it == 0 && lin_hit) {
+                // (the rows went to G' after the tightening)
+#pragma unroll
+                for (int i = 0; i < NX; ++i) F[i] = lin_F[i];
+            } else if (it == 0 && lin_hit) {
                 // the first SQP iteration linearises at the stored iterate: identical rows
                 for (int e = lane; e < H * NX * GS; e += 64) L.G[e] = lin_b[e];
 #pragma unroll

@@ -6,7 +6,7 @@ set -e
 NAME=$1; DEFS=$2
 cd "$(dirname "$0")/../gp-mpc_amd/csrc"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -mllvm -amdgpu-mfma-vgpr-form=1"
-mkdir -p build/v_$NAME
+mkdir -p build/v_$NAME ../gpmpc/lib
 TS=("")
 [ -n "${TIMING_TOO:-}" ] && TS=("" timing)   # TIMING_TOO=1: also the phase-stamp build
 for t in "${TS[@]}"; do
