@@ -68,6 +68,7 @@ struct gpmpc_handle {
     int32_t* has_prev = nullptr;
     double* lin = nullptr;          // linearisation cache of the stored iterate (StateDev::lin)
     int32_t* lin_tag = nullptr;
+    int32_t* t_prev = nullptr;      // reference index of each instance's last good solve (StateDev::t_prev)
     bool lin_cache = true;          // GPMPC_TUNE_LIN_CACHE
     int32_t* order = nullptr;       // cost-ordered dispatch (StateDev::order / cost)
     uint32_t* cost = nullptr;
@@ -224,6 +225,7 @@ static void free_handle(gpmpc_handle* h) {
         if (p) (void)hipFree(p);
     if (h->has_prev) (void)hipFree(h->has_prev);
     if (h->lin_tag) (void)hipFree(h->lin_tag);
+    if (h->t_prev) (void)hipFree(h->t_prev);
     if (h->order) (void)hipFree(h->order);
     if (h->cost) (void)hipFree(h->cost);
     if (h->scratch_i) (void)hipFree(h->scratch_i);
@@ -318,6 +320,14 @@ gpmpc_status gpmpc_create(int32_t model_id, int32_t horizon, int32_t max_batch, 
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ncu = 0;
         P.n_cu = ncu;
     }
+    // t_prev = -1: no instance has a solve to shift from (GPMPC_TUNE_SHIFT)
+    e = hipMalloc((void**)&h->t_prev, B * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(h->t_prev, 0xff, B * sizeof(int32_t));
+    if (e != hipSuccess) {
+        free_handle(h);
+        return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    P.shift = 0;            // one-stage shifted warm start (GPMPC_TUNE_SHIFT)
     const size_t lds = sqp_lds_bytes(model_id, horizon);
     if (lds > 160 * 1024) {
         free_handle(h);
@@ -610,6 +620,7 @@ gpmpc_status gpmpc_reset(gpmpc_handle* h, int32_t batch, int32_t reset_iterate, 
     HIPCHK(order_after_last(h, s));
     StreamMark mark{h, s};
     HIPCHK(hipMemsetAsync(h->has_prev, 0, B * sizeof(int32_t), s));
+    HIPCHK(hipMemsetAsync(h->t_prev, 0xff, B * sizeof(int32_t), s));   // -1: nothing to shift from
     bump_lin(h);
     if (reset_iterate) {
         HIPCHK(hipMemsetAsync(h->x, 0, B * (H + 1) * h->md.nx * sizeof(double), s));
@@ -633,6 +644,7 @@ gpmpc_status gpmpc_set_iterate(gpmpc_handle* h, int32_t batch, const double* x_d
     HIPCHK(hipMemcpyAsync(h->x, x_dev, B * (H + 1) * h->md.nx * sizeof(double), hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(h->u, u_dev, B * H * h->md.nu * sizeof(double), hipMemcpyDeviceToDevice, s));
     bump_lin(h);
+    HIPCHK(hipMemsetAsync(h->t_prev, 0xff, B * sizeof(int32_t), s));   // -1: an explicit guess is not shifted
     HIPCHK(hipMemsetAsync(h->pi, 0, B * H * h->md.nx * sizeof(double), s));
     HIPCHK(hipMemsetAsync(h->lam, 0, B * (H + 1) * 2 * h->nb * sizeof(double), s));
     return GPMPC_OK;
@@ -695,7 +707,7 @@ gpmpc_status gpmpc_solve(gpmpc_handle* h, int32_t batch, const double* x0, const
         return launch_gp_post_batch(pb, true, st);
     };
     StateDev S{h->x, h->u, h->pi, h->lam, h->has_prev, h->var, h->tight, h->lin_cache ? h->lin : nullptr, h->lin_tag,
-               h->order, h->cost, 0};
+               h->order, h->cost, 0, h->t_prev};
     StepIO io{x0, tstep, u0, status, sqp_iter, qp_iter, res, h->timing, h->stats};
     // optional outputs go to handle-owned scratch when NULL
     if (!io.sqp_iter) io.sqp_iter = h->scratch_i;
@@ -933,6 +945,10 @@ gpmpc_status gpmpc_set_tuning(gpmpc_handle* h, int32_t option, int32_t value) {
         case GPMPC_TUNE_TAIL:
             if (value < -1 || value > 16384) break;
             h->tail = value;
+            return GPMPC_OK;
+        case GPMPC_TUNE_SHIFT:
+            if (value != 0 && value != 1) break;
+            h->P.shift = value;
             return GPMPC_OK;
         case GPMPC_TUNE_EVENT_FENCE:
             if (value != 0 && value != 1) break;

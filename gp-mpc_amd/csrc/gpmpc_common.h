@@ -91,6 +91,10 @@ struct ProblemDev {
     // the boundary chain's pivot threshold relative to Ph's largest diagonal entry (gpmpc_set_tuning
     // GPMPC_TUNE_SEG_PIVOT): below it the solve falls back to the one-segment recursion
     double seg_piv_rel;
+    // one-stage shifted warm start (gpmpc_set_tuning GPMPC_TUNE_SHIFT): an instance whose previous
+    // solve ended good at reference index t_prev starts this one, at tstep = t_prev + 1 (mod
+    // traj_len), from the stored iterate and multipliers moved up one stage (StateDev::t_prev)
+    int32_t shift;
     GPDev gp[kMaxGP];
 };
 
@@ -122,6 +126,9 @@ struct StateDev {
     // rank of this launch's first workgroup in order[] (a launch over ranks first .. first + grid - 1:
     // the two halves of an overlapped step, capi.hip gpmpc_solve); 0 otherwise
     int32_t first;
+    // reference index (tstep mod traj_len) of the instance's last solve when it ended good, -1 after
+    // a failed one, a reset or gpmpc_set_iterate: the eligibility test of ProblemDev::shift.  [B]
+    int32_t* t_prev;
 };
 
 struct StepIO {

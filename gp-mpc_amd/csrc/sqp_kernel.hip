@@ -3100,7 +3100,18 @@ struct SqpKernel {
         // valid when the step that stored the iterate also stored them and no host call since has
         // changed the iterate, the GPs or the model (lin_tag == lin_gen)
         double* lin_b = S.lin ? S.lin + (size_t)b * H * NX * GS : nullptr;
-        const bool lin_hit = lin_b != nullptr && P.lin_gen != 0 &&
+        // one-stage shifted warm start (ProblemDev::shift): this solve follows the instance's last good
+        // one by exactly one reference index, so it starts from that solution moved up one stage (the
+        // block after the tightening).  The cached rows 1 .. H - 1 are the linearisation of the shifted
+        // stages 0 .. H - 2, but the shifted last stage (x_H, u_{H-1}) was never linearised and a
+        // linearisation pass costs the same for one stage as for H, so every model and horizon
+        // recomputes on a shifted step (no cache hit; stats slot 9 counts it).
+        bool sh = false;
+        if (P.shift != 0) {
+            const int tp = __builtin_amdgcn_readfirstlane(S.t_prev[b]);
+            sh = tp >= 0 && io.tstep[b] % P.traj_len == (tp + 1) % P.traj_len;
+        }
+        const bool lin_hit = lin_b != nullptr && P.lin_gen != 0 && !sh &&
                              __builtin_amdgcn_readfirstlane(S.lin_tag[b]) == P.lin_gen;
         // GPMPC_LIN_EARLY: the cached rows of the first SQP iteration are loaded here, into registers,
         // and go to G' after the tightening, so their round trip runs under its arithmetic (split
@@ -3307,6 +3318,44 @@ struct SqpKernel {
                     const int e = lane + 64 * j;
                     if (e < H * NX * GS) L.G[e] = lin_r[j];
                 }
+            }
+        }
+        // ---------------- shifted warm start: the SQP starts from stage min(k + 1, last) of the stored
+        // solution (the terminal stage duplicated); the tightening above, the variance launch and
+        // gpmpc_get_solution read the unshifted one.  Multiplier rows move with their variable (x_0 has
+        // none).  Multipliers kept in global memory are shifted in place, one variable group at a time:
+        // lane k reads row k + 1 and then writes row k, and a group's reads (the whole wave's) complete
+        // before its writes issue; they are this solve's to overwrite (a good exit stores its own, a
+        // failed one zeroes them).
+        if (sh) {
+            const int kx = min(k + 1, H), ku = min(k + 1, H - 1);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) w[i] = on ? xg[kx * NX + i] : 0.0;
+#pragma unroll
+            for (int a = 0; a < NU; ++a) w[NX + a] = act_u ? ug[ku * NU + a] : 0.0;
+            const double* lam_x = S.lam + ((size_t)b * (H + 1) + (act_x ? kx : k)) * 2 * NB;
+            const double* lam_u = S.lam + ((size_t)b * (H + 1) + (act_u ? ku : k)) * 2 * NB;
+            const double* pi_s = S.pi + ((size_t)b * H + (act_u ? ku : 0)) * NX;
+            if (on) {
+                double t[2 * NX];
+#pragma unroll
+                for (int i = 0; i < NX; ++i) { t[i] = lam_x[i]; t[NX + i] = lam_x[NB + i]; }
+#pragma unroll
+                for (int i = 0; i < NX; ++i) { lam_l[i] = t[i]; lam_l[NB + i] = t[NX + i]; }
+            }
+            if (on) {
+                double t[2 * NU];
+#pragma unroll
+                for (int a = 0; a < NU; ++a) { t[a] = lam_u[NX + a]; t[NU + a] = lam_u[NB + NX + a]; }
+#pragma unroll
+                for (int a = 0; a < NU; ++a) { lam_l[NX + a] = t[a]; lam_l[NB + NX + a] = t[NU + a]; }
+            }
+            if (act_u) {
+                double t[NX];
+#pragma unroll
+                for (int i = 0; i < NX; ++i) t[i] = pi_s[i];
+#pragma unroll
+                for (int i = 0; i < NX; ++i) pi_l[i] = t[i];
             }
         }
         if (S.tight != nullptr && on) {
@@ -3568,6 +3617,7 @@ struct SqpKernel {
             for (int q = 0; q < 4; ++q) io.res[(size_t)b * 4 + q] = res[q];
             S.has_prev[b] = good ? 1 : 0;
             if (lin_b != nullptr) S.lin_tag[b] = good ? P.lin_gen : 0;
+            if (S.t_prev != nullptr) S.t_prev[b] = good ? io.tstep[b] % P.traj_len : -1;
             if (S.cost != nullptr)   // this solve's work, for the next launch's dispatch order
                 S.cost[b] = (uint32_t)(kCostLin * it + 2 * qp_total);
             if (io.stats != nullptr) {

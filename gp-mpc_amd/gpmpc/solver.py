@@ -53,11 +53,15 @@ def _c(a) -> np.ndarray:
 
 
 class BatchSolver:
-    """One solver handle for ``batch`` instances of ``spec`` with horizon ``horizon``."""
+    """One solver handle for ``batch`` instances of ``spec`` with horizon ``horizon``.
+
+    ``warm_start_shift=True`` turns on the one-stage shifted warm start (``set_tuning(shift=1)``);
+    ``GPMPC`` and ``MPC`` pass it through their solver keywords."""
 
     def __init__(self, spec: ModelSpec, horizon: int, batch: int, device="cuda", prior_params: dict | None = None,
                  traj: np.ndarray | None = None, uh: float = -1e-8, cost_scaling: bool = True, max_iter: int = 25,
-                 tol: float = 1e-6, qp_max_iter: int = 50, qp_tol: float | None = None, qp_mu0: float = 1.0):
+                 tol: float = 1e-6, qp_max_iter: int = 50, qp_tol: float | None = None, qp_mu0: float = 1.0,
+                 warm_start_shift: bool = False):
         self.lib = _lib.load()
         self.spec = spec
         self.H = int(horizon)
@@ -76,6 +80,9 @@ class BatchSolver:
         self.set_options(max_iter=max_iter, tol=tol, qp_max_iter=qp_max_iter, qp_tol=qp_tol, qp_mu0=qp_mu0)
         self.set_reference(spec.reference_trajectory() if traj is None else traj)
         self.set_var_inputs(spec.var_inputs)
+        self.tuning: dict[str, int] = {}   # options set through set_tuning (the others are on their default)
+        if warm_start_shift:
+            self.set_tuning(shift=1)
         self.gps: list[GaussianProcess] | None = None
         # per-step device buffers
         kw = dict(device=self.device)
@@ -214,11 +221,20 @@ class BatchSolver:
 
     def set_tuning(self, **opts):
         """Performance switches (gpmpc_set_tuning): lin_cache=0/1, order=0/1/2, overlap=0/1,
-        var_split=0/1/4, event_fence=0/1, seg=0/1, tail=K, seg_pivot=k.  Outputs do not depend on them (A/B knobs)."""
+        var_split=0/1/4, event_fence=0/1, seg=0/1, tail=K, seg_pivot=k.  Outputs do not depend on them (A/B knobs).
+
+        shift=0/1 is the exception.  With 1, an instance whose previous solve ended with status 0 or 2
+        and whose ``tstep`` has advanced by exactly one (modulo the reference length) starts its SQP
+        from the stored solution and multipliers moved up one stage, the terminal stage duplicated;
+        every other solve (first, after ``reset`` / ``set_iterate``, after a failed solve, repeated or
+        jumped ``tstep``) runs as with 0.  The tightening and ``solution()`` still use the unshifted
+        stored solution, so the converged result agrees to the solver tolerance while ``sqp_iter`` /
+        ``qp_iter`` change; such a solve recomputes its first linearisation.  Default 0."""
         for k, v in opts.items():
             if k not in _lib.TUNE:
                 raise ValueError(f"unknown tuning option {k!r} (one of {sorted(_lib.TUNE)})")
             _lib.check(self.lib.gpmpc_set_tuning(self._h, _lib.TUNE[k], int(v)))
+            self.tuning[k] = int(v)
 
     def set_cost_output(self, enabled: bool = True) -> torch.Tensor | None:
         """Per-stage LINEAR_LS costs of every solve's new solution into ``self.stage_cost`` (B, H+1)

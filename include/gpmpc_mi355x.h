@@ -123,7 +123,8 @@ gpmpc_status gpmpc_set_var_inputs(gpmpc_handle* h, int32_t gp_id, const int32_t*
  * AcadosOcpSolver GPMPC.reset builds after new GPs, gpmpc/gpmpc.py:97-108). */
 gpmpc_status gpmpc_reset(gpmpc_handle* h, int32_t batch, int32_t reset_iterate, void* stream);
 
-/* Set the warm-start iterate (device arrays x [B][H+1][nx], u [B][H][nu]); multipliers zeroed. */
+/* Set the warm-start iterate (device arrays x [B][H+1][nx], u [B][H][nu]); multipliers zeroed.
+ * The next solve starts from exactly this guess (GPMPC_TUNE_SHIFT does not move it). */
 gpmpc_status gpmpc_set_iterate(gpmpc_handle* h, int32_t batch, const double* x_dev, const double* u_dev, void* stream);
 
 /* One batched control step: GPMPC.select_action(obs) for every instance
@@ -209,8 +210,8 @@ gpmpc_status gpmpc_get_launch_info(gpmpc_handle* h, int32_t batch, int32_t* wave
 gpmpc_status gpmpc_get_launch_segments(gpmpc_handle* h, int32_t batch, int32_t* segments);
 
 /* Performance switches (no reference counterpart; every output is bit-identical or identical up
- * to rounding whichever value is set -- A/B measurement knobs, all on their default after
- * gpmpc_create).  gpmpc_set_tuning(h, option, value):
+ * to rounding whichever value is set, GPMPC_TUNE_SHIFT excepted -- A/B measurement knobs, all on
+ * their default after gpmpc_create).  gpmpc_set_tuning(h, option, value):
  *   GPMPC_TUNE_LIN_CACHE   1 (default): the first SQP iteration of a step reads the stored
  *                          iterate's linearisation; 0: recompute it (bit-identical)
  *   GPMPC_TUNE_ORDER       1 (default): a launch needing more than one round of workgroups runs
@@ -237,7 +238,23 @@ gpmpc_status gpmpc_get_launch_segments(gpmpc_handle* h, int32_t batch, int32_t* 
  *   GPMPC_TUNE_SEG_PIVOT   10 (default): the segment solve's boundary chain refuses a pivot below
  *                          10^-value x Ph's largest diagonal entry and redoes that Newton solve as
  *                          the one-segment recursion; -1: refuses every pivot (every segment solve
- *                          takes that fallback: a test of it) */
+ *                          takes that fallback: a test of it)
+ *   GPMPC_TUNE_SHIFT       0 (default): every solve starts from the stored iterate and multipliers
+ *                          at the same stage index; 1: one-stage shifted warm start.  An instance
+ *                          whose previous gpmpc_solve ended good (status 0 or 2) at reference index
+ *                          t and whose tstep now equals (t + 1) mod L starts its SQP from stage
+ *                          min(k + 1, last) of the stored x, u, dynamics and bound multipliers (the
+ *                          terminal stage duplicated, not rolled out), the window its reference has
+ *                          moved to.  Every other instance -- first solve, after gpmpc_reset or
+ *                          gpmpc_set_iterate, after a failed solve, a repeated or jumped tstep --
+ *                          runs exactly as with 0.  Only the SQP's start point moves: the tightening,
+ *                          its variance launch and gpmpc_get_solution read the unshifted stored
+ *                          solution, so each step's NLP is unchanged.  Outputs are NOT identical up
+ *                          to rounding under this option: the converged solution agrees with the
+ *                          unshifted one to the solver tolerance and the iteration path (sqp_iter,
+ *                          qp_iter, a status-2 iterate) differs.  A shifted solve recomputes its
+ *                          first linearisation (the cache holds no row for the duplicated last
+ *                          stage).  Any other value: GPMPC_ERR_ARG */
 enum {
     GPMPC_TUNE_LIN_CACHE = 0,
     GPMPC_TUNE_ORDER = 1,
@@ -246,7 +263,8 @@ enum {
     GPMPC_TUNE_EVENT_FENCE = 4,
     GPMPC_TUNE_SEG = 5,
     GPMPC_TUNE_TAIL = 6,
-    GPMPC_TUNE_SEG_PIVOT = 7
+    GPMPC_TUNE_SEG_PIVOT = 7,
+    GPMPC_TUNE_SHIFT = 8
 };
 gpmpc_status gpmpc_set_tuning(gpmpc_handle* h, int32_t option, int32_t value);
 
