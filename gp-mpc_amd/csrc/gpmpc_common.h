@@ -174,16 +174,34 @@ __device__ __forceinline__ size_t post_row(const PostArgs& a, int p) {
     return (size_t)a.order[a.first + r] * a.H + (p - r * a.H);
 }
 
-// exp(x) for the RBF kernel, x <= 0 and finite: Cody-Waite reduction x = n ln2 + r, |r| <= ln2/2,
-// degree-11 Chebyshev fit of exp on [-ln2/2, ln2/2] (mpmath chebyfit, fit error 3.2e-18; max
-// relative error of this f64 evaluation 1 ulp on a 2e5-point grid), scale by 2^n.  n comes from
-// the magic-number rounding t = x log2(e) + 1.5 2^52 (one fma; the low word of t is n in two's
-// complement) and 2^n is applied by an integer add to the exponent field of p, so the f64 work
-// is 15 operations instead of 17 (rint, cvt and ldexp gone).  n is clamped at -1022 for the
-// scaling: below exp(-708) the result is p 2^-1022 (< 3e-308) instead of a denormal or 0.
-// No overflow/NaN guards: the argument is -0.5 q/ell^2.
+// exp(x) for the RBF kernel, total on x <= 0 (-inf included): Cody-Waite reduction x = n ln2 + r,
+// |r| <= ln2/2, degree-11 Chebyshev fit of exp on [-ln2/2, ln2/2] (mpmath chebyfit, fit error
+// 3.2e-18; max relative error of this f64 evaluation 1 ulp on a 2e5-point grid), scale by 2^n.
+// n comes from the magic-number rounding t = x log2(e) + 1.5 2^52 (one fma; the low word of t is
+// n in two's complement) and 2^n is applied by an integer add to the exponent field of p, so the
+// f64 work is 15 operations instead of 17 (rint, cvt and ldexp gone).  The argument is clamped
+// first, so that n >= -1022 always: without a clamp the low word of t wraps below
+// -2^31 ln2 = -1.49e9 (a query 1.1e4 lengthscales from a training row) and the exponent add returns
+// huge or negative values.  The clamp is one 32-bit integer operation on the high word of x
+// (exp_rbf_clamp: a negative double's magnitude grows with its high word read as unsigned), in
+// place of the integer max(n, -1022) the scaling had before, so the operation count is the same.
+// It heads the dependent chain, where that max sat beside it: the headline benchmark measured
+// 0.7 % slower with it (2.790 -> 2.769 M), and 1.2 % slower with an f64 max(x, -1022 ln2) instead.
+// An argument whose high word exceeds kExpRbfHiMin, i.e. x < -708.39648 (-inf and negative NaNs
+// included), takes that high word and keeps its low word: it lands in [-708.39698, -708.39648],
+// where n = -1022 and p < 1, and gives about 2^-1022 (2.2e-308) instead of a denormal or 0.
+// Every x >= -708.39648, which includes all x >= -1022 ln2 = -708.39642, is untouched and gives
+// what the routine gave before, bit for bit; below exp(-708.2) the result is under 3e-308 but not
+// correctly rounded.
+// No overflow / positive-NaN guards: the argument is -0.5 q/ell^2 (or its centred expansion, which
+// can round a few ulp above 0).
+constexpr unsigned kExpRbfHiMin = 0xC086232Cu;   // high word of -708.396484375 (one step past -1022 ln2's)
+__device__ __forceinline__ double exp_rbf_clamp(double x) {
+    return __hiloint2double((int)min((unsigned)__double2hiint(x), kExpRbfHiMin), __double2loint(x));
+}
 __device__ __forceinline__ double exp_rbf(double x) {
     constexpr double kMagic = 6755399441055744.0;   // 1.5 * 2^52
+    x = exp_rbf_clamp(x);
     const double t = fma(x, 1.4426950408889634, kMagic);
     const double n = t - kMagic;
     double r = fma(n, -6.93147180369123816490e-01, x);
@@ -200,8 +218,7 @@ __device__ __forceinline__ double exp_rbf(double x) {
     p = fma(p, r, 0.5000000000000019);
     p = fma(p, r, 1.0);
     p = fma(p, r, 1.0);
-    const int ni = max(__double2loint(t), -1022);
-    return __hiloint2double(__double2hiint(p) + (ni << 20), __double2loint(p));
+    return __hiloint2double(__double2hiint(p) + (__double2loint(t) << 20), __double2loint(p));
 }
 
 // exp_rbf of K independent arguments, written step by step across the K values.  One wave
@@ -218,6 +235,8 @@ __device__ __forceinline__ void exp_rbf_n(double (&x)[K]) {
                               0.5000000000000019, 1.0, 1.0};
     double t[K], r[K], p[K];
 #pragma unroll
+    for (int k = 0; k < K; ++k) x[k] = exp_rbf_clamp(x[k]);
+#pragma unroll
     for (int k = 0; k < K; ++k) t[k] = fma(x[k], 1.4426950408889634, kMagic);
 #pragma unroll
     for (int k = 0; k < K; ++k) r[k] = fma(t[k] - kMagic, -6.93147180369123816490e-01, x[k]);
@@ -230,10 +249,8 @@ __device__ __forceinline__ void exp_rbf_n(double (&x)[K]) {
 #pragma unroll
         for (int k = 0; k < K; ++k) p[k] = fma(p[k], r[k], c[i]);
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int ni = max(__double2loint(t[k]), -1022);
-        x[k] = __hiloint2double(__double2hiint(p[k]) + (ni << 20), __double2loint(p[k]));
-    }
+    for (int k = 0; k < K; ++k)
+        x[k] = __hiloint2double(__double2hiint(p[k]) + (__double2loint(t[k]) << 20), __double2loint(p[k]));
 }
 
 // Up to kMaxGP posterior evaluations in one launch (grid.y = GP).

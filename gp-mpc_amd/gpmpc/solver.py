@@ -178,6 +178,27 @@ class BatchSolver:
                                                grad.data_ptr(), self._stream()))
         return mean, grad
 
+    def gp_predict(self, gp_id: int, z: torch.Tensor, with_noise: bool = False, mean: bool = True, var: bool = True):
+        """Posterior mean (P,) and exact variance (P,) of the handle's GP ``gp_id`` at z (P, d)
+        (gpmpc_gp_predict; ``with_noise`` adds the likelihood noise to the variance).  ``mean`` /
+        ``var``: True allocates the output, False leaves it out (None is returned in its place), a
+        contiguous float64 tensor of at least P elements on the solver's device is written in place.
+        The variance needs the GP's Linv (``with_variance``)."""
+        z = z.to(self.device, torch.float64).contiguous()
+        P = z.shape[0]
+
+        def out(o):
+            if isinstance(o, torch.Tensor):
+                if o.dtype != torch.float64 or o.device != self.device or not o.is_contiguous() or o.numel() < P:
+                    raise ValueError(f"output must be a contiguous float64 tensor of >= {P} elements on {self.device}")
+                return o
+            return torch.empty(P, dtype=torch.float64, device=self.device) if o else None
+
+        m, v = out(mean), out(var)
+        _lib.check(self.lib.gpmpc_gp_predict(self._h, int(gp_id), z.data_ptr(), P, _lib.ptr(m), _lib.ptr(v),
+                                             int(with_noise), self._stream()))
+        return m, v
+
     def set_var_inputs(self, var_inputs):
         """Per-GP input map of the tightening variance (indices into z = [x; u]); see
         gpmpc_set_var_inputs.  ``spec.var_inputs`` (the reference's map) is the default."""

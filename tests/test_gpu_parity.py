@@ -125,6 +125,11 @@ def test_gp_predict_edge_cases():
     far = np.array([[1e3, 1e3, 1e3]])  # far from the data: mean 0, variance sf2
     m, v = gpp[1].predict(torch.tensor(far, device="cuda"), with_noise=False)
     assert abs(float(m[0])) < 1e-12 and abs(float(v[0]) - hyp[1][1]) < 1e-12
+    # further than the reduction of exp_rbf could index before its argument was clamped (the kernel's
+    # exponent is -3.75e11 and -3.75e15 here): mean 0 or subnormal-small, variance sf2
+    for dist in (1e6, 1e8):
+        m, v = gpp[1].predict(torch.full((1, 3), dist, dtype=torch.float64, device="cuda"), with_noise=False)
+        assert abs(float(m[0])) < 1e-290 and abs(float(v[0]) - hyp[1][1]) < 1e-12, (dist, float(m[0]), float(v[0]))
 
 
 @pytest.mark.parametrize("name,N,H,B,steps,M,love", [("quad2d", 200, 30, 4, 3, None, False),
