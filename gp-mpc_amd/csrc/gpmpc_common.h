@@ -10,7 +10,7 @@ constexpr int kMaxGPDim = 3;    // inputs per GP (packed rows are 4 doubles: x0,
 constexpr int kMaxNX = 12;
 constexpr int kMaxNU = 4;
 constexpr int kMaxH = 63;       // one lane per stage 0..H (64-lane wavefront)
-constexpr int kPhases = 12;  // diagnostic phase slots (GPMPC_TIMING builds)
+constexpr int kPhases = 15;  // diagnostic phase slots (GPMPC_TIMING builds; sqp_kernel.hip TPHASE)
 constexpr int kMaxParams = 16;
 constexpr int kStatsSlots = 12;  // per-instance solver statistics (gpmpc_set_stats_buffer, = GPMPC_STATS_SLOTS)
 

@@ -39,6 +39,9 @@
 #ifndef GPMPC_LIN_EARLY   // 1: cached linearisation rows loaded before the tightening arithmetic (A/B variants: 0)
 #define GPMPC_LIN_EARLY 1
 #endif
+#ifndef GPMPC_CORR_DELTA   // 1: the IPM corrector solves for the change of the affine step (right-hand side: the change of gq, no dynamics residual), one-wave single-tile MFMA kernels (A/B variants: 0 = the full re-solve)
+#define GPMPC_CORR_DELTA 1
+#endif
 #ifndef GPMPC_PHASE_LANE   // (round-6 A/B of phase_lane: 0 off, 1 one-wave and quad3d kernels, 2 every kernel)
 #define GPMPC_PHASE_LANE 1
 #endif
@@ -65,8 +68,16 @@ __device__ __forceinline__ void wave_sync() {
 // Diagnostic phase timing (build with -DGPMPC_TIMING): shader-clock cycles per phase,
 // accumulated by the wave and stored per instance.  Phases (kPhases): 0 tightening, 1 linearise,
 // 2 residuals/QP setup, 3 IPM vector work, 4 Riccati factor, 5 Riccati vector, 6 forward sweeps,
-// 7 other, 8 closed-loop maps, 9 step recovery, 10 IPM residuals/Newton data.
+// 7 other, 8 closed-loop maps, 9 step recovery, 10 IPM residuals/Newton data, 11 GP sums (inside 1);
+// phase 2 in parts: 12 SQP step update, multiplier and reference loads (TPHASE_LOADS: the stamp waits
+// for the loads, so their exposed latency is counted there), 13 residual norms, 14 QP set-up and cold
+// start.
 #ifdef GPMPC_TIMING
+#define TPHASE_LOADS(id)                                             \
+    do {                                                             \
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); \
+        TPHASE(id);                                                  \
+    } while (0)
 #define TPHASE(id)                                                   \
     do {                                                             \
         const unsigned long long t_ = __builtin_amdgcn_s_memtime();  \
@@ -76,6 +87,7 @@ __device__ __forceinline__ void wave_sync() {
     } while (0)
 #else
 #define TPHASE(id) do { } while (0)
+#define TPHASE_LOADS(id) do { } while (0)
 #endif
 
 // ------------------------------------------------------------------ cross-lane moves (gfx950)
@@ -345,6 +357,12 @@ struct SqpKernel {
     // (NX x NX at PXL) and K'_k = [K | kff | K_lambda] (row stride KST).
     static constexpr bool kSeg = SEG;
     static_assert(!SEG || (NW >= 2 && NB + 1 <= 16 && NX + 1 <= 8), "segment-parallel solve: single-tile models on >= 2 waves");
+    // Delta corrector (GPMPC_CORR_DELTA): the predictor and the corrector of an IPM iteration share the
+    // factorisation and the dynamics residual, so the corrector solves the same system for the change
+    // of gq alone (c = 0, dx_0 = 0) and adds the result to the affine step.  One-wave kernels only:
+    // the multi-wave MFMA kernels without segments measured 0.5 % slower with it (their scratch frame
+    // grew by 80-160 B/lane); the segment path and quad3d's two-tile path keep the full re-solve too.
+    static constexpr bool kCorrDelta = GPMPC_CORR_DELTA != 0 && kMfma && !SEG && NW == 1;
     static constexpr int LI = 8 + NU;
     static_assert(!SEG || LI + NX <= 16, "lambda slots in the 16-wide tile");
     static constexpr int KST = SEG ? 2 * NX + 1 : PS;          // K' row stride
@@ -1176,7 +1194,7 @@ struct SqpKernel {
     }
 
     // Closed-loop stage maps A'_k = [A + B K | B kff + c] (all stages in parallel); only the
-    // affine column when the factorisation is unchanged (corrector).
+    // affine column when the factorisation is unchanged (corrector; kCorrDelta: B kff).
     template <bool full>
     __device__ static void acl_phase(const Lds& L, int H, int lane) {
         lane = phase_lane(lane);
@@ -1215,9 +1233,15 @@ struct SqpKernel {
                     const int k = e / NX, i = e - k * NX;
                     const double* G = L.G + (size_t)k * NX * GS + i * GS;
                     const double* Kk = L.K + (size_t)k * NU * PS;
-                    acc[r] = G[NB];
+                    if constexpr (kCorrDelta) {   // the delta system has no dynamics residual: B_k kff_k
+                        acc[r] = G[NX] * Kk[NX];
 #pragma unroll
-                    for (int a = 0; a < NU; ++a) acc[r] = fma(G[NX + a], Kk[a * PS + NX], acc[r]);
+                        for (int a = 1; a < NU; ++a) acc[r] = fma(G[NX + a], Kk[a * PS + NX], acc[r]);
+                    } else {
+                        acc[r] = G[NB];
+#pragma unroll
+                        for (int a = 0; a < NU; ++a) acc[r] = fma(G[NX + a], Kk[a * PS + NX], acc[r]);
+                    }
                 }
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
@@ -1304,17 +1328,19 @@ struct SqpKernel {
     // with [q; r] = gq.  Only the p recurrence is sequential (one v_mfma_f64_4x4x4_4b + DPP merge per
     // stage, mfma4_stage); t_k = P_{k+1} c_k and vt_k are built for all stages in parallel.
     // Scratch: t aliases hq (rewritten before the next factorisation), vt aliases dxv.
+    // kCorrDelta: gq is the change of the gradient and c = 0, so the t pass is gone and vt_k, kff_k lose
+    // their t terms; p, kff (and the forward sweep after them) are then those of the delta step.
     __device__ static void mfma4_vector_backward(const Lds& L, int H, int lane) {
         lane = phase_lane(lane);
-        double* T = L.hq;
-        double* VT = L.dxv;
+        [[maybe_unused]] double* T = L.hq;
+        [[maybe_unused]] double* VT = L.dxv;
         // entries (k, i) two per pass, both computed before either is stored (T and VT alias other
         // LDS buffers, so a store would otherwise order the next entry's reads behind it)
         // (each pass issues every load of its entries before a scheduling barrier: loads interleaved
         // with their uses issue a few at a time)
         const int n = H * NX;
         struct TOps { double pr[NX], gc[NX]; };
-        auto t_load = [&](int e, TOps& o) {
+        [[maybe_unused]] auto t_load = [&](int e, TOps& o) {
             const int k = e / NX, i = e - k * NX;
             const double* Pn = L.P + (size_t)(k + 1) * PP;
             const double* G = L.G + (size_t)k * NX * GS;
@@ -1324,28 +1350,32 @@ struct SqpKernel {
                 o.gc[l] = G[l * GS + NB];
             }
         };
-        auto t_dot = [](const TOps& o) {
+        [[maybe_unused]] auto t_dot = [](const TOps& o) {
             double acc = 0.0;
 #pragma unroll
             for (int l = 0; l < NX; ++l) acc = fma(o.pr[l], o.gc[l], acc);
             return acc;
         };
-        for (int e0 = lane; e0 < n; e0 += 128) {
-            const int e1 = e0 + 64;
-            const bool has1 = e1 < n;
-            TOps o0, o1;
-            t_load(e0, o0);
-            t_load(has1 ? e1 : e0, o1);
-            __builtin_amdgcn_sched_barrier(0);
-            const double a0 = t_dot(o0), a1 = t_dot(o1);
-            T[e0] = a0;
-            if (has1) T[e1] = a1;
+        if constexpr (!kCorrDelta) {
+            for (int e0 = lane; e0 < n; e0 += 128) {
+                const int e1 = e0 + 64;
+                const bool has1 = e1 < n;
+                TOps o0, o1;
+                t_load(e0, o0);
+                t_load(has1 ? e1 : e0, o1);
+                __builtin_amdgcn_sched_barrier(0);
+                const double a0 = t_dot(o0), a1 = t_dot(o1);
+                T[e0] = a0;
+                if (has1) T[e1] = a1;
+            }
+            WSYNC();
         }
-        WSYNC();
-        struct VOps { double g0, gu[NU], kc[NU], ac[NX], tk[NX]; };
+        // kCorrDelta: gq holds the change of the gradient and the system has no dynamics residual, so
+        // t_k = 0 and vt_k = q_k + K_k^T r_k
+        struct VOps { double g0, gu[NU], kc[NU], ac[kCorrDelta ? 1 : NX], tk[kCorrDelta ? 1 : NX]; };
         auto vt_load = [&](int e, VOps& o) {
             const int k = e / NX, i = e - k * NX;
-            const double* A = L.Acl + (size_t)k * NX * PS;
+            [[maybe_unused]] const double* A = L.Acl + (size_t)k * NX * PS;
             const double* Kk = L.K + (size_t)k * NU * PS;
             o.g0 = L.gq[k * NBS + i];
 #pragma unroll
@@ -1353,18 +1383,22 @@ struct SqpKernel {
                 o.kc[a] = Kk[a * PS + i];
                 o.gu[a] = L.gq[k * NBS + NX + a];
             }
+            if constexpr (!kCorrDelta) {
 #pragma unroll
-            for (int l = 0; l < NX; ++l) {
-                o.ac[l] = A[l * PS + i];
-                o.tk[l] = T[k * NX + l];
+                for (int l = 0; l < NX; ++l) {
+                    o.ac[l] = A[l * PS + i];
+                    o.tk[l] = T[k * NX + l];
+                }
             }
         };
         auto vt_dot = [](const VOps& o) {
             double acc = o.g0;
 #pragma unroll
             for (int a = 0; a < NU; ++a) acc = fma(o.kc[a], o.gu[a], acc);
+            if constexpr (!kCorrDelta) {
 #pragma unroll
-            for (int l = 0; l < NX; ++l) acc = fma(o.ac[l], o.tk[l], acc);
+                for (int l = 0; l < NX; ++l) acc = fma(o.ac[l], o.tk[l], acc);
+            }
             return acc;
         };
         for (int e0 = lane; e0 < n; e0 += 128) {
@@ -1420,7 +1454,7 @@ struct SqpKernel {
                 for (int l = 0; l < NX; ++l) gb[b2][l] = G[l * GS + NX + b2];
             }
 #pragma unroll
-            for (int l = 0; l < NX; ++l) tp[l] = T[k * NX + l] + pn[l];
+            for (int l = 0; l < NX; ++l) tp[l] = kCorrDelta ? pn[l] : T[k * NX + l] + pn[l];
             __builtin_amdgcn_sched_barrier(0);
             double kf = 0.0;
 #pragma unroll
@@ -1435,7 +1469,9 @@ struct SqpKernel {
         WSYNC();
     }
 
-    // Per-lane step from the MFMA Riccati solution (packed P').
+    // Per-lane step from the MFMA Riccati solution (packed P').  ADD (kCorrDelta, corrector): dpi is
+    // added to the affine step's, which qp_ipm left in hq (its loads go out with this function's own).
+    template <bool ADD = false>
     __device__ static void recover_step_mfma(const Lds& L, int H, int lane, double (&dd)[NB], double (&dpi)[NX]) {
         lane = phase_lane(lane);
         const bool on = lane <= H;
@@ -1462,12 +1498,18 @@ struct SqpKernel {
         double pp[PP];
 #pragma unroll
         for (int q = 0; q < PP; ++q) pp[q] = Pn[q];
+        [[maybe_unused]] double da[NX];
+        if constexpr (ADD) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) da[i] = L.hq[kk * NBS + i];
+        }
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
             double acc = pp[NX * (NX + 1) / 2 + i];
 #pragma unroll
             for (int j = 0; j < NX; ++j) acc = fma(pp[i <= j ? pidx(i, j) : pidx(j, i)], dxn[j], acc);
-            dpi[i] = (lane < H) ? -acc : 0.0;
+            if constexpr (ADD) dpi[i] = (lane < H) ? da[i] - acc : 0.0;
+            else dpi[i] = (lane < H) ? -acc : 0.0;
         }
     }
 
@@ -2538,11 +2580,12 @@ struct SqpKernel {
     }
 
     // Step of stage kq from the Riccati solution, restricted to this lane's variables, and dpi_kq.
-    template <int NV>
+    template <int NV, bool ADD = false>
     __device__ static void recover_q(const Lds& L, int H, int kq, int vb, double (&dd)[NV], double (&dp)[NX]) {
         double ddf[NB];
+        static_assert(!ADD || kCorrDelta, "the delta corrector's recovery");
         if constexpr (kSeg) recover_step_seg(L, H, kq, ddf, dp);
-        else if constexpr (kMfma) recover_step_mfma(L, H, kq, ddf, dp);
+        else if constexpr (kMfma) recover_step_mfma<ADD>(L, H, kq, ddf, dp);
         else recover_step(L, H, kq, ddf, dp);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
@@ -2807,6 +2850,15 @@ struct SqpKernel {
                     if (!rok) { qp_ok = false; break; }
                     TPHASE(9);
                     recover_q<NV>(L, H, kq, vb, dd, dp);
+                    if constexpr (kCorrDelta) {
+                        // the affine dynamics-multiplier step waits in hq for the corrector's recovery (the
+                        // factorisation has consumed hq, and the delta form keeps no t_k there): NX more
+                        // live doubles per lane across the solve put the one-wave kernel into scratch
+                        if (actu_q && !hi_half) {
+#pragma unroll
+                            for (int i = 0; i < NX; ++i) L.hq[kq * NBS + i] = dp[i];
+                        }
+                    }
                     TPHASE(3);
                 } else {
                     // the recursion on wave 0 (WSPL: the other waves wait at the status exchange)
@@ -2851,17 +2903,24 @@ struct SqpKernel {
                 const double sr = mu_aff / mu;
                 const double smu = sr * sr * sr * mu;
                 // corrector: r_ml = ll sl + dll_aff dsl_aff - sigma mu  ->  gq += (dll dsl - smu)/sl - (dlu dsu - smu)/su
+                // (kCorrDelta: the change alone, 0 for this lane's inactive variables -- the corrector
+                // solves for the change of the affine step)
                 double dda[NV];
 #pragma unroll
                 for (int j = 0; j < NV; ++j) {
                     dda[j] = dd[j];
+                    double dg = 0.0;
                     if (on_q && avq(j)) {
                         const double rl = d[j] - blo[j] - sl[j];
                         const double ru = bup[j] - d[j] - su[j];
                         const double dsl = dd[j] + rl, dsu = -dd[j] + ru;
                         const double dll = -ll[j] * fma(dsl, isl[j], 1.0);
                         const double dlu = -lu[j] * fma(dsu, isu[j], 1.0);
-                        L.gq[k_q * NBS + vb + j] += (dll * dsl - smu) * isl[j] - (dlu * dsu - smu) * isu[j];
+                        dg = (dll * dsl - smu) * isl[j] - (dlu * dsu - smu) * isu[j];
+                        if constexpr (!kCorrDelta) L.gq[k_q * NBS + vb + j] += dg;
+                    }
+                    if constexpr (kCorrDelta) {
+                        if (on_q && vb + j < NB) L.gq[k_q * NBS + vb + j] = dg;
                     }
                 }
                 XSYNC();
@@ -2883,8 +2942,12 @@ struct SqpKernel {
                     }
                     XSYNC();
                     TPHASE(9);
-                    recover_q<NV>(L, H, kq, vb, dd, dp);
+                    recover_q<NV, kCorrDelta>(L, H, kq, vb, dd, dp);   // (kCorrDelta: dp = affine + change)
                     TPHASE(3);
+                    if constexpr (kCorrDelta) {   // affine step + its change
+#pragma unroll
+                        for (int j = 0; j < NV; ++j) dd[j] = dda[j] + dd[j];
+                    }
                 } else {
                     if (wv == 0) {
                         valu_vector_big(L, H, lane);
@@ -3412,13 +3475,14 @@ struct SqpKernel {
                 linearize(P, L, H, lane, w, F, tgp);
             }
             WSYNC();
-            TPHASE(2);
+            TPHASE(12);
             // stage reference (gpmpc.py:356-361)
             double yr[NB];
 #pragma unroll
             for (int i = 0; i < NX; ++i) yr[i] = P.traj[(size_t)tref * NX + i];
 #pragma unroll
             for (int a = 0; a < NU; ++a) yr[NX + a] = P.u_eq[a];
+            TPHASE_LOADS(13);
             // NLP residuals with the current multipliers
             double ct[NB];
             ctpi(L, H, lane, pi, ct);
@@ -3463,6 +3527,7 @@ struct SqpKernel {
                 break;
             }
             if (it == P.max_iter) { status = kMaxIter; lin_store(F); break; }
+            TPHASE(14);
 
             // ---------------- QP in the step variables (HPIPM's role): qp_ipm
             // qv(): variable vb + j of stage kq from a stage vector held in the lane = stage layout.
@@ -3525,7 +3590,7 @@ struct SqpKernel {
             const bool qp_ok = qp_ipm<SPL, NV>(P, L, H, lane, 0, blo, bup, gv, hd, d, cqq, ll, lu, piq, qit, tm);
             if constexpr (WSPL) qp_publish_step<NV>(L, H, lane, 0, d);   // B2: the full step in Dq
             qp_total += qit;
-            TPHASE(2);
+            TPHASE(12);
             if (!qp_ok) { status = kQPFailure; break; }
             // full SQP step: w += d, multipliers <- QP multipliers
             if (on_q) {

@@ -21,7 +21,12 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 PHASES = ["tighten", "linearize", "resid/setup", "ipm-vector", "ric-factor", "ric-vector", "forward", "other",
-          "acl-maps", "recover", "ipm-resid", "(gp-sums within linearize)"]
+          "acl-maps", "recover", "ipm-resid"]
+# slots after the phases (kPhases in gpmpc_common.h = len(PHASES) + len(SUBS)): the GP sums are timed inside
+# "linearize"; the kernel stamps "resid/setup" in three parts, which are added up into that phase here
+SUBS = ["(gp-sums within linearize)", "(resid/setup: step, mult/ref loads)", "(resid/setup: residual norms)",
+        "(resid/setup: QP set-up)"]
+NSLOT = len(PHASES) + len(SUBS)
 
 
 def main():
@@ -76,7 +81,7 @@ def main():
         s.set_gps(gps, fitc=fitc)
         s.set_tightening(True, 0.95, *mats)
     s.reset(True)
-    tbuf = torch.zeros(B, len(PHASES), dtype=torch.int64, device="cuda")
+    tbuf = torch.zeros(B, NSLOT, dtype=torch.int64, device="cuda")
     _lib.check(s.lib.gpmpc_set_timing_buffer(s._h, tbuf.data_ptr()))
     traj = spec.reference_trajectory()
     x0, ph = initial_states(spec, traj, B)
@@ -85,8 +90,9 @@ def main():
     for _ in range(args.warmup):
         u0 = s.solve(obs, ts)
         s.plant_step(obs, u0, ts, out=obs)
-    tot = np.zeros(len(PHASES))
-    crit = np.zeros(len(PHASES))   # the slowest instance of each step (it sets the kernel time)
+    NP = len(PHASES)
+    tot = np.zeros(NSLOT)
+    crit = np.zeros(NSLOT)   # the slowest instance of each step (it sets the kernel time)
     per_step = []
     s.set_profiling(True)
     s.kernel_times()
@@ -94,27 +100,29 @@ def main():
         u0 = s.solve(obs, ts)
         torch.cuda.synchronize()
         tb = tbuf.cpu().numpy().astype(np.float64)
+        tb[:, 2] += tb[:, NP + 1:].sum(1)   # the parts of "resid/setup"
         per_step.append(tb.copy())
         tot += tb.mean(0)
-        crit += tb[np.argmax(tb[:, :-1].sum(1))]
+        crit += tb[np.argmax(tb[:, :NP].sum(1))]
         s.plant_step(obs, u0, ts, out=obs)
     kt = s.kernel_times()
     if args.dump:
         np.save(args.dump, np.stack(per_step))
     cyc = tot / args.steps
-    sub = cyc[-1]            # GP sums: a sub-phase of "linearize", not part of the total
-    cyc = cyc[:-1]
+    sub = cyc[NP:]           # sub-phases: parts of a phase, not part of the total
+    cyc = cyc[:NP]
     ms = kt["sqp_ms"] / max(kt["sqp_launches"], 1)
     print(f"waves {args.waves or 'auto'}")
     print(f"{spec.name} B={B} H={H} N={N}: sqp kernel {ms:.3f} ms/launch, sqp_iter {s.sqp_iter.float().mean():.2f}, "
           f"qp_iter {s.qp_iter.float().mean():.2f}")
     print(f"cycles per instance (mean) {cyc.sum():.0f} -> {cyc.sum() / (ms * 1e-3) / 1e9:.2f} G cycles/s effective")
     crit /= args.steps
-    csub, crit = crit[-1], crit[:-1]
+    csub, crit = crit[NP:], crit[:NP]
     print(f"{'phase':26s} {'mean instance':>22s} {'slowest instance per step':>30s}")
     for name, c, k in zip(PHASES, cyc, crit):
         print(f"  {name:24s} {c:10.0f} cyc {100 * c / cyc.sum():5.1f} %   {k:10.0f} cyc {100 * k / crit.sum():5.1f} %")
-    print(f"  {PHASES[-1]:24s} {sub:10.0f} cyc {100 * sub / cyc.sum():5.1f} %   {csub:10.0f} cyc {100 * csub / crit.sum():5.1f} %")
+    for name, c, k in zip(SUBS, sub, csub):
+        print(f"  {name:36s} {c:10.0f} cyc {100 * c / cyc.sum():5.1f} %   {k:10.0f} cyc {100 * k / crit.sum():5.1f} %")
     print(f"  {'total':24s} {cyc.sum():10.0f} cyc           {crit.sum():10.0f} cyc")
 
 
