@@ -82,6 +82,13 @@ struct gpmpc_handle {
     double* gp_linvT[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
     double* gp_tiles[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};   // tX | tW (MFMA tile pack)
     int gp_npad[kMaxGP] = {0, 0, 0, 0};
+    // appending (gpmpc_gp_reserve / gpmpc_gp_append): training rows the GP's buffers hold (the uploaded
+    // size until reserved), whether the upload was exact (Xv == X), the second factor buffer the
+    // factor moves to when npad grows (the two swap roles), and the append kernels' scratch
+    int gp_cap[kMaxGP] = {0, 0, 0, 0};
+    bool gp_exact[kMaxGP] = {false, false, false, false};
+    double* gp_linvT_alt[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
+    double* gp_app[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
     double* gp_vroot[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};   // LOVE roots (tightening only)
     int gp_vroot_cols[kMaxGP] = {0, 0, 0, 0};
     int gp_vroot_rank[kMaxGP] = {0, 0, 0, 0};
@@ -236,6 +243,8 @@ static void free_handle(gpmpc_handle* h) {
         if (h->gp_linvT[g]) (void)hipFree(h->gp_linvT[g]);
         if (h->gp_tiles[g]) (void)hipFree(h->gp_tiles[g]);
         if (h->gp_vroot[g]) (void)hipFree(h->gp_vroot[g]);
+        if (h->gp_linvT_alt[g]) (void)hipFree(h->gp_linvT_alt[g]);
+        if (h->gp_app[g]) (void)hipFree(h->gp_app[g]);
     }
     delete h;
 }
@@ -455,7 +464,8 @@ gpmpc_status gpmpc_set_gp(gpmpc_handle* h, int32_t gp_id, int32_t n, int32_t d, 
         for (int j = 0; j < 4; ++j) tW[(size_t)t * 64 + (grp * 4 + j) * 4 + q] = wv[j];
     }
     for (double** p : {&h->gp_rows[gp_id], &h->gp_vrows[gp_id], &h->gp_linvT[gp_id], &h->gp_tiles[gp_id],
-                       &h->gp_vroot[gp_id]}) {   // (a LOVE root belongs to the previous training set)
+                       &h->gp_vroot[gp_id], &h->gp_linvT_alt[gp_id],
+                       &h->gp_app[gp_id]}) {   // (a LOVE root belongs to the previous training set)
         if (*p) HIPCHK(hipFree(*p));
         *p = nullptr;
     }
@@ -491,8 +501,151 @@ gpmpc_status gpmpc_set_gp(gpmpc_handle* h, int32_t gp_id, int32_t n, int32_t d, 
     g.sf2 = outputscale;
     g.sn2 = noise;
     h->gp_npad[gp_id] = npad;
+    h->gp_cap[gp_id] = n;   // (appending needs gpmpc_gp_reserve)
+    h->gp_exact[gp_id] = exact;
     h->gp_set[gp_id] = true;
     bump_lin(h);
+    return GPMPC_OK;
+}
+
+// Scratch of the append kernels for a capacity of cpad rows (GPAppend): W^T [16][cpad] | per-tile
+// means [cpad/16][16] | L_b^-1 [256] | beta [16] | status word
+static size_t app_scratch_doubles(int cpad) { return (size_t)16 * cpad + cpad + 256 + 16 + 1; }
+
+gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
+    if (!h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
+    if (!h->gp_exact[gp_id]) return fail(GPMPC_ERR_STATE, "FITC upload (Xv != X): only an exact GP takes appended rows");
+    GPDev& g = h->P.gp[gp_id];
+    if (capacity < g.n) return fail(GPMPC_ERR_ARG, "capacity below the GP's " + std::to_string(g.n) + " training rows");
+    if (capacity > (1 << 15)) return fail(GPMPC_ERR_ARG, "capacity above 32768 rows");
+    (void)hipSetDevice(h->device);
+    HIPCHK(hipDeviceSynchronize());   // a setup call: nothing queued still reads the buffers replaced below
+    const size_t cpad = ((size_t)capacity + 15) / 16 * 16, ct = cpad / 16;
+    const size_t npad = h->gp_npad[gp_id], nt = g.ntile;
+    const bool lin = h->gp_linvT[gp_id] != nullptr;
+    // everything is allocated and filled before the handle changes
+    double *rows = nullptr, *tiles = nullptr, *la = nullptr, *lb = nullptr, *app = nullptr;
+    auto drop = [&]() {
+        for (double* p : {rows, tiles, la, lb, app})
+            if (p) (void)hipFree(p);
+    };
+    hipError_t e = hipMalloc(&rows, cpad * 4 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&tiles, 2 * ct * 64 * sizeof(double));
+    if (e == hipSuccess && lin) e = hipMalloc(&la, cpad * cpad * sizeof(double));
+    if (e == hipSuccess && lin) e = hipMalloc(&lb, cpad * cpad * sizeof(double));
+    if (e == hipSuccess && lin) e = hipMalloc(&app, app_scratch_doubles((int)cpad) * sizeof(double));
+    if (e != hipSuccess) {
+        drop();
+        return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    e = hipMemset(rows, 0, cpad * 4 * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(tiles, 0, 2 * ct * 64 * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(rows, h->gp_rows[gp_id], npad * 4 * sizeof(double), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy(tiles, g.tX, nt * 64 * sizeof(double), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy(tiles + ct * 64, g.tW, nt * 64 * sizeof(double), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && lin) e = hipMemset(app, 0, app_scratch_doubles((int)cpad) * sizeof(double));
+    // the factor keeps its stride npad (the variance kernels' layout) at the head of the first buffer
+    if (e == hipSuccess && lin)
+        e = hipMemcpy(la, h->gp_linvT[gp_id], npad * npad * sizeof(double), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        drop();
+        return fail(GPMPC_ERR_HIP, std::string("gpmpc_gp_reserve: ") + hipGetErrorString(e));
+    }
+    for (double** p : {&h->gp_rows[gp_id], &h->gp_tiles[gp_id], &h->gp_linvT[gp_id], &h->gp_linvT_alt[gp_id],
+                       &h->gp_app[gp_id]}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    h->gp_rows[gp_id] = rows;
+    h->gp_tiles[gp_id] = tiles;
+    h->gp_linvT[gp_id] = la;
+    h->gp_linvT_alt[gp_id] = lb;
+    h->gp_app[gp_id] = app;
+    g.rows = g.vrows = rows;
+    g.linvT = la;
+    g.tX = tiles;
+    g.tW = tiles + ct * 64;
+    h->gp_cap[gp_id] = capacity;
+    bump_lin(h);
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_size(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* capacity) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
+    if (!h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
+    if (n) *n = h->P.gp[gp_id].n;
+    if (capacity) *capacity = h->gp_cap[gp_id];
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const double* Xnew_dev, const double* ynew_dev,
+                             int32_t* accepted_dev, void* stream) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
+    if (m < 1 || !Xnew_dev || !ynew_dev) return fail(GPMPC_ERR_ARG, "no rows to append");
+    if (!h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
+    if (!h->gp_exact[gp_id]) return fail(GPMPC_ERR_STATE, "FITC upload (Xv != X): only an exact GP takes appended rows");
+    if (!h->gp_linvT[gp_id]) return fail(GPMPC_ERR_STATE, "append needs Linv (the GP was set without it)");
+    if (h->gp_vroot[gp_id])
+        return fail(GPMPC_ERR_STATE, "a LOVE root is installed: it belongs to the old training set (drop it first, "
+                                     "gpmpc_set_gp_variance_root with R = NULL)");
+    GPDev& g = h->P.gp[gp_id];
+    if ((int64_t)g.n + m > h->gp_cap[gp_id])
+        return fail(GPMPC_ERR_ARG, "capacity exceeded: " + std::to_string(g.n) + " + " + std::to_string(m) +
+                                       " rows, capacity " + std::to_string(h->gp_cap[gp_id]) + " (gpmpc_gp_reserve)");
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const int cpad = (h->gp_cap[gp_id] + 15) / 16 * 16, d = h->md.gp_dim[gp_id];
+    double* app = h->gp_app[gp_id];
+    for (int done = 0, blk = 0; done < m; done += 16, ++blk) {
+        const int mb = std::min(16, m - done);
+        const int n0 = g.n, npad0 = h->gp_npad[gp_id], npad1 = (n0 + mb + 15) / 16 * 16;
+        // the model changes with the first launch queued: the cache must not serve its old rows
+        bump_lin(h);
+        if (npad1 > npad0) {
+            // the factor moves to the other buffer at the new stride, the new border zeroed
+            double* dst = h->gp_linvT_alt[gp_id];
+            const size_t p0 = (size_t)npad0 * sizeof(double), p1 = (size_t)npad1 * sizeof(double);
+            HIPCHK(hipMemcpy2DAsync(dst, p1, h->gp_linvT[gp_id], p0, p0, npad0, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemset2DAsync(dst + npad0, p1, 0, p1 - p0, npad0, s));
+            HIPCHK(hipMemsetAsync(dst + (size_t)npad0 * npad1, 0, (size_t)(npad1 - npad0) * p1, s));
+            std::swap(h->gp_linvT[gp_id], h->gp_linvT_alt[gp_id]);
+            g.linvT = h->gp_linvT[gp_id];
+            h->gp_npad[gp_id] = npad1;
+        }
+        GPAppend a{};
+        a.rows = h->gp_rows[gp_id];
+        a.tX = h->gp_tiles[gp_id];
+        a.tW = h->gp_tiles[gp_id] + (size_t)(cpad / 16) * 64;
+        a.linvT = h->gp_linvT[gp_id];
+        a.npad = npad1;
+        a.n0 = n0;
+        a.m = mb;
+        a.d = d;
+        for (int k = 0; k < 3; ++k) a.xbar[k] = g.xbar[k];
+        a.inv_ell2 = g.inv_ell2;
+        a.sf2 = g.sf2;
+        a.sn2 = g.sn2;
+        a.Xnew = Xnew_dev + (size_t)done * d;
+        a.ynew = ynew_dev + done;
+        a.wt = app;
+        a.ldw = cpad;
+        a.pmean = app + (size_t)16 * cpad;
+        a.lbinv = a.pmean + cpad;
+        a.beta = a.lbinv + 256;
+        a.flag = reinterpret_cast<int32_t*>(a.beta + 16);
+        a.accepted = accepted_dev ? accepted_dev + blk : nullptr;
+        HIPCHK(launch_gp_append(a, s));
+        // the row count advances whether the block is accepted or written as inert rows
+        g.n = g.nv = n0 + mb;
+        g.ntile = (g.n + 15) / 16;
+    }
     return GPMPC_OK;
 }
 

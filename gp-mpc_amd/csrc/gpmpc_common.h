@@ -266,7 +266,33 @@ struct PostBatch {
     int32_t var_split;
 };
 
-// Launchers (sqp_kernel.hip, gp_kernels.hip).
+// One block of m <= 16 rows appended to an exact GP (gp_append.hip; gpmpc_gp_append fills it per block).
+struct GPAppend {
+    double* rows;         // [>= npad][4], GPDev::rows (rows past n0 are zero)
+    double* tX;           // GPDev::tX / tW (capacity-sized regions)
+    double* tW;
+    double* linvT;        // [npad][npad], the factor at the stride this block leaves it with
+    int32_t npad;         // n0 + m rounded up to 16
+    int32_t n0;           // rows before the block
+    int32_t m;            // rows of the block
+    int32_t d;
+    double xbar[3];       // the tile pack's centre (unchanged by appends)
+    double inv_ell2, sf2, sn2;
+    const double* Xnew;   // [m][d] (device)
+    const double* ynew;   // [m]
+    // scratch of the GP: W^T [16][ldw], per-tile means at X_b [ntile][16], L_b^-1 [16][16], beta [16],
+    // the block's status (1 accepted, 0 written as inert rows)
+    double* wt;
+    int32_t ldw;
+    double* pmean;
+    double* lbinv;
+    double* beta;
+    int32_t* flag;
+    int32_t* accepted;    // the caller's status word of this block, may be null
+};
+
+// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip).
+hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream);
 // count < 0: the whole batch; else ranks first .. first + count - 1 of order[] (launch_sqp_order)
 hipError_t launch_sqp(const ProblemDev& P, const StateDev& S, const StepIO& io, int batch, hipStream_t stream,
                       int first = 0, int count = -1);

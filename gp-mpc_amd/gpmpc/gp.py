@@ -90,6 +90,23 @@ class GaussianProcess:
         self.K, self.K_inv, self._dev = None, None, None
         return self
 
+    def append_data(self, x: torch.Tensor, y: torch.Tensor):
+        """Extend the training set by rows x (m, d), y (m,), hyperparameters unchanged.  The cached
+        covariances and device layout are dropped, so a later ``device_layout`` / ``fit_gp`` sees
+        all data (the solver handle's copy is extended by ``BatchSolver.append_gp``)."""
+        X = self.train_inputs[0]
+        x = torch.as_tensor(x).to(X.device, torch.float64)
+        if x.ndim == 1:
+            x = x[:, None] if self.input_dimension == 1 else x[None, :]
+        y = torch.as_tensor(y).to(X.device, torch.float64).reshape(-1)
+        if x.shape[1] != self.input_dimension or y.shape[0] != x.shape[0]:
+            raise ValueError(f"expected x (m, {self.input_dimension}) and y (m,), got {tuple(x.shape)} and {tuple(y.shape)}")
+        self.train_inputs = (torch.cat([X, x]),)
+        self.train_targets = torch.cat([self.train_targets, y])
+        self.n_ind_points = self.train_inputs[0].shape[0]
+        self.K, self.K_inv, self._dev = None, None, None
+        return self
+
     def parameters(self):
         return [self.raw_lengthscale, self.raw_outputscale, self.raw_noise]
 

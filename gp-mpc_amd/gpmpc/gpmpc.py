@@ -36,7 +36,7 @@ class GPMPC:
                  horizon: int = 25, q_mpc: list | None = None, r_mpc: list | None = None, sparse_gp: bool = False,
                  prob: float = 0.955, max_gp_samples: int = 30, seed: int = 1337, device: str = "cuda",
                  output_dir: Path | None = None, batch: int = 1, variance_inputs: str = "reference",
-                 variance: str = "love", **solver_kw):
+                 variance: str = "love", gp_capacity: int | None = None, **solver_kw):
         spec = (symbolic_model if isinstance(symbolic_model, ModelSpec) else get_spec(symbolic_model)).copy()
         # "reference": the variance input map of `gpmpc/gpmpc.py:437-444` (for quad3d it indexes the
         # full state-input vector with the GP-input-space indices); "dynamics": each GP's own inputs
@@ -81,6 +81,9 @@ class GPMPC:
         self.max_gp_samples = max_gp_samples
         self.Bd = spec.bd_matrix()
         self.batch = int(batch)
+        # training rows the solver handle's GPs get room for when they are uploaded (reset()), so that
+        # append_data can extend them on the device; None: the uploaded size (no appending)
+        self.gp_capacity = None if gp_capacity is None else int(gp_capacity)
 
         self.prior_ctrl = MPC(spec, traj=self.traj, horizon=self.T, q_mpc=list(spec.q_diag),
                               r_mpc=list(spec.r_diag), device=device, batch=batch, **solver_kw)
@@ -184,6 +187,34 @@ class GPMPC:
         self.gaussian_process = gps
         self._requires_recompile = True
 
+    def append_data(self, inputs: np.ndarray, targets: np.ndarray) -> list[torch.Tensor]:
+        """Fold new observations into the uploaded GPs between two control steps, hyperparameters
+        unchanged: ``inputs`` (m, sum d_g) and ``targets`` (m, n_gp) in GP-input space, as
+        ``preprocess_data`` returns them.  Every GP on the solver handle is extended on the device
+        (``BatchSolver.append_gp``, queued on the current stream) and the Python GP objects with it
+        (``GaussianProcess.append_data``), so a later ``train_gp`` refit or upload sees all data.
+        Returns the accepted flags per GP (device tensors).  Needs room (``gp_capacity``); not
+        available in sparse (FITC) mode, whose inducing weights belong to the old training set."""
+        if self.sparse:
+            raise _lib.GPMPCError("append_data: not available in sparse (FITC) mode")
+        assert self.gaussian_process is not None and not self._requires_recompile, \
+            "GP model must be uploaded (call reset())"
+        inputs = np.atleast_2d(np.asarray(inputs, dtype=np.float64))
+        targets = np.atleast_2d(np.asarray(targets, dtype=np.float64))
+        if inputs.shape[1] != sum(self.model.gp_dims) or targets.shape != (inputs.shape[0], self.model.n_gp):
+            raise ValueError(f"expected inputs (m, {sum(self.model.gp_dims)}) and targets (m, {self.model.n_gp})")
+        n, cap = self.solver.gp_size(0)
+        if n + inputs.shape[0] > cap:   # before any GP changes, so the handle's GPs stay in step
+            raise _lib.GPMPCError(f"append_data: capacity exceeded ({n} + {inputs.shape[0]} rows, capacity {cap}; "
+                                  "construct GPMPC with gp_capacity)")
+        flags = []
+        for i, idx in enumerate(self.gp_idx):
+            X = torch.tensor(inputs[:, idx], device=self.device)
+            y = torch.tensor(targets[:, i], device=self.device)
+            flags.append(self.solver.append_gp(i, X, y))
+            self.gaussian_process[i].append_data(X, y)
+        return flags
+
     def precompute_sparse_posterior_mean(self, n_samples: int):
         """FITC weights on random training rows (`gpmpc/gpmpc.py:377-400`), computed where the
         GP lives (the MI355X for a GP fitted by ``train_gp``)."""
@@ -219,6 +250,9 @@ class GPMPC:
                 n = self.gaussian_process[0].train_targets.shape[0]
                 fitc = self.precompute_sparse_posterior_mean(min(n, self.max_gp_samples))
             self.solver.set_gps(self.gaussian_process, with_variance=True, fitc=fitc, variance=self.variance)
+            if self.gp_capacity is not None and not self.sparse:
+                for g in range(self.model.n_gp):   # (a training set already past the capacity stays as uploaded)
+                    self.solver.reserve_gp(g, max(self.gp_capacity, self.solver.gp_size(g)[0]))
             self._requires_recompile = False
             # new GPs: the reference builds a fresh AcadosOcpSolver (`gpmpc/gpmpc.py:97-108`), whose
             # memory -- iterate and multipliers -- starts from zero

@@ -6,6 +6,9 @@ synthetic plant kernel (``BatchSolver.plant_step``: RK4 of the model with its tr
 parameters), so B episodes run at once on the GPU; transitions are gathered from all of them.
 
 * :func:`run_evaluation` -- one closed-loop episode per instance (`run_gp_mpc.py:42-72`)
+* :func:`run_online_episode` -- the same episode, learning while it runs: a few of every step's
+  transitions are appended to the uploaded GPs on the device (``GPMPC.append_data``); no
+  counterpart in the reference, whose loop is episodic
 * :func:`sample_data`    -- random transitions of an episode batch (`run_gp_mpc.py:75-83`)
 * :func:`learn`          -- prior run, then per epoch: sample, ``preprocess_data``,
   ``train_gp`` (on the GPU; data-parallel under torch.distributed), ``reset``, test and
@@ -52,6 +55,42 @@ def run_evaluation(ctrl, x0: np.ndarray, steps: int, tstep0: np.ndarray | None =
         data["status"].append(ctrl.solver.status.cpu().numpy())
         obs = solver.plant_step(obs, u, ts)   # advances the reference index too
         data["obs"].append(obs.cpu().numpy())
+    return {k: np.array(v) for k, v in data.items()}
+
+
+def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, seed: int,
+                       tstep0: np.ndarray | None = None) -> dict:
+    """A closed-loop episode that learns while it runs: after every plant step a seeded random
+    choice of ``append_per_step`` of the step's B transitions is preprocessed
+    (``GPMPC.preprocess_data``) and appended to the uploaded GPs (``GPMPC.append_data``, a
+    bordered Cholesky update on the device), until the GPs' capacity (``gp_capacity``) is reached;
+    the next control step runs on the extended model.  Hyperparameters stay as trained.  Returns
+    the dict of :func:`run_evaluation` plus ``n_train`` (steps,), the training rows after each step."""
+    ctrl.reset()
+    solver = ctrl.solver
+    dev = solver.device
+    B = solver.batch
+    rng = np.random.default_rng(seed)
+    obs = torch.tensor(np.asarray(x0, dtype=np.float64).reshape(B, -1), device=dev)
+    ts = torch.tensor(np.zeros(B) if tstep0 is None else tstep0, dtype=torch.int32, device=dev)
+    data = {"obs": [obs.cpu().numpy()], "action": [], "status": [], "inference_time_data": [], "n_train": []}
+    for _ in range(steps):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        u = ctrl.select_action_batch(obs, ts.clone())
+        torch.cuda.synchronize(dev)
+        data["inference_time_data"].append(time.perf_counter() - t0)
+        data["action"].append(u.cpu().numpy())
+        data["status"].append(solver.status.cpu().numpy())
+        obs = solver.plant_step(obs, u, ts)   # advances the reference index too
+        data["obs"].append(obs.cpu().numpy())
+        n, cap = solver.gp_size(0)
+        pick = rng.choice(B, min(append_per_step, B), replace=False)[:max(cap - n, 0)]
+        if len(pick):
+            inputs, targets = ctrl.preprocess_data(data["obs"][-2][pick], data["action"][-1][pick],
+                                                   data["obs"][-1][pick])
+            ctrl.append_data(inputs, targets)
+        data["n_train"].append(solver.gp_size(0)[0])
     return {k: np.array(v) for k, v in data.items()}
 
 

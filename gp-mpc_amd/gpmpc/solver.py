@@ -167,6 +167,38 @@ class BatchSolver:
         _lib.check(self.lib.gpmpc_use_gp(self._h, 1))
         self.gps = gps
 
+    def reserve_gp(self, gp_id: int, capacity: int):
+        """Room for up to ``capacity`` training rows of the handle's GP ``gp_id`` (gpmpc_gp_reserve;
+        after ``set_gps``, which resets the capacity to the uploaded size; a synchronous setup call)."""
+        _lib.check(self.lib.gpmpc_gp_reserve(self._h, int(gp_id), int(capacity)))
+
+    def append_gp(self, gp_id: int, X, y) -> torch.Tensor:
+        """Append training rows X (m, d), y (m,) to the handle's GP ``gp_id`` on the current stream
+        (gpmpc_gp_append): one bordered-Cholesky update per block of up to 16 rows, hyperparameters
+        unchanged.  cuda or host tensors (or arrays); no synchronisation of its own.  Returns the
+        accepted flags, a device int32 tensor with one entry per block (1 accepted, 0 written as
+        inert rows).  The Python GP objects are not touched (``GaussianProcess.append_data``)."""
+        X = torch.as_tensor(X).to(self.device, torch.float64)
+        y = torch.as_tensor(y).to(self.device, torch.float64).reshape(-1).contiguous()
+        if X.ndim == 1:
+            X = X[:, None]
+        X = X.contiguous()
+        m, d = X.shape
+        if y.shape[0] != m:
+            raise ValueError("X and y disagree on the number of rows")
+        if d != self.spec.gp_dims[int(gp_id)]:
+            raise ValueError(f"GP {gp_id} takes inputs of dimension {self.spec.gp_dims[int(gp_id)]}, got {d}")
+        flags = torch.empty((m + 15) // 16, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gpmpc_gp_append(self._h, int(gp_id), m, X.data_ptr(), y.data_ptr(), flags.data_ptr(),
+                                            self._stream()))
+        return flags
+
+    def gp_size(self, gp_id: int) -> tuple[int, int]:
+        """(training rows, capacity) of the handle's GP ``gp_id`` (gpmpc_gp_size)."""
+        n, cap = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(self.lib.gpmpc_gp_size(self._h, int(gp_id), ctypes.byref(n), ctypes.byref(cap)))
+        return n.value, cap.value
+
     def gp_mean_grad(self, gp_id: int, z: torch.Tensor):
         """GP mean (P,) and input gradient (P, d) at z (P, d) through the linearisation's MFMA tile
         sums (the casadi mean + AD of `gpmpc/gp.py:72-85`, `gpmpc/gpmpc.py:189-209`)."""

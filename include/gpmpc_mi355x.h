@@ -99,6 +99,34 @@ gpmpc_status gpmpc_set_gp(gpmpc_handle* h, int32_t gp_id, int32_t n, int32_t d, 
  * gpmpc_gp_predict / gpmpc_gp_posterior stay exact. */
 gpmpc_status gpmpc_set_gp_variance_root(gpmpc_handle* h, int32_t gp_id, int32_t n, int32_t r, const double* R);
 
+/* Appending training rows on the device (no refactorisation, no host round trip): for an exact GP
+ * uploaded with Linv, a block of m <= 16 new rows is one bordered Cholesky update of (L^-1)^T and
+ * alpha = K^-1 y (csrc/gp_append.hip), with the hyperparameters unchanged.  The MFMA tile pack of
+ * the mean rows (tW lane order as gpmpc_set_gp builds it: for row i = 16t + r, lane group r % 4,
+ * register r / 4, columns [alpha, alpha (x - xbar)]) is rewritten for every row, centred on the
+ * xbar gpmpc_set_gp computed: the centring is algebraically exact for any xbar and only conditions
+ * the exponent, so xbar is not moved.
+ *
+ * Make room for up to `capacity` training rows of GP gp_id (after gpmpc_set_gp; contents kept;
+ * synchronous setup call).  gpmpc_set_gp resets the capacity to the uploaded size. */
+gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity);
+
+/* Append m >= 1 training rows (device: Xnew [m][d], ynew [m]) to GP gp_id on `stream`: blocks of
+ * up to 16 rows, each one bordered-Cholesky update; no host synchronisation.
+ * accepted_dev: device int32 [ceil(m/16)], 1 / 0 per block, may be NULL.  A block with a
+ * non-finite input or target, or whose Schur complement has a pivot that is not finite and
+ * positive, is written as inert rows (zero input, zero weight, zero factor row and column, like
+ * padding: they add nothing to any mean or variance, now or after later appends) and reports 0;
+ * the old weights are left alone and the row count advances either way.
+ * Refused, with the GP unchanged: n + m above the capacity (GPMPC_ERR_ARG); GP not set, set
+ * without Linv, a FITC upload (Xv != X), or a LOVE root installed -- it belongs to the old
+ * training set, drop it first with gpmpc_set_gp_variance_root(R = NULL) (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const double* Xnew_dev,
+                             const double* ynew_dev, int32_t* accepted_dev, void* stream);
+
+/* Training rows of GP gp_id (inert rows included) and its capacity; either may be NULL. */
+gpmpc_status gpmpc_gp_size(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* capacity);
+
 /* Enable (1) / disable (0) the GP residual in the dynamics: 0 = nominal MPC
  * (gpmpc/mpc.py, prior dynamics only). */
 gpmpc_status gpmpc_use_gp(gpmpc_handle* h, int32_t enabled);
