@@ -15,6 +15,12 @@ using namespace gpmpc;
 
 static_assert(GPMPC_STATS_SLOTS == kStatsSlots, "public stats-slot count must match the kernel's");
 
+// A new handle's GPMPC_TUNE_VAR_TRIM (a variant build with -DGPMPC_VAR_TRIM_DEFAULT=0 runs the
+// benchmark, which has no switch for it, on the untrimmed variance kernel)
+#ifndef GPMPC_VAR_TRIM_DEFAULT
+#define GPMPC_VAR_TRIM_DEFAULT 1
+#endif
+
 namespace {
 thread_local std::string g_err;
 
@@ -121,6 +127,7 @@ struct gpmpc_handle {
     // forked from and joined back into the caller's stream by two events
     bool overlap = true;            // GPMPC_TUNE_OVERLAP
     int var_split = 0;              // GPMPC_TUNE_VAR_SPLIT
+    bool var_trim = GPMPC_VAR_TRIM_DEFAULT != 0;   // GPMPC_TUNE_VAR_TRIM
     bool event_fence = false;       // GPMPC_TUNE_EVENT_FENCE
     double* stage_cost = nullptr;   // caller's [max_batch][H+1] stage-cost buffer (StepIO::stage_cost)
     hipStream_t side = nullptr;
@@ -832,6 +839,7 @@ gpmpc_status gpmpc_solve(gpmpc_handle* h, int32_t batch, const double* x0, const
         pb.n = h->md.ngp;
         pb.step_points = batch * h->H;
         pb.var_split = h->var_split;
+        pb.var_full = h->var_trim ? 0 : 1;
         for (int g = 0; g < h->md.ngp; ++g) {
             PostArgs& a = pb.a[g];
             a.sx = h->x;
@@ -1086,6 +1094,10 @@ gpmpc_status gpmpc_set_tuning(gpmpc_handle* h, int32_t option, int32_t value) {
             if (value != 0 && value != 1 && value != 4) break;
             h->var_split = value;
             return GPMPC_OK;
+        case GPMPC_TUNE_VAR_TRIM:
+            if (value != 0 && value != 1) break;
+            h->var_trim = value == 1;
+            return GPMPC_OK;
         case GPMPC_TUNE_SEG:
             if (value != 0 && value != 1) break;
             h->P.seg = value;
@@ -1256,7 +1268,7 @@ gpmpc_status gpmpc_gp_predict(gpmpc_handle* h, int32_t gp_id, const double* Z, i
     if (var) {
         a.mean = nullptr;
         a.var = var;
-        HIPCHK(launch_gp_post(g, h->gp_npad[gp_id], a, false, (hipStream_t)stream));
+        HIPCHK(launch_gp_post(g, h->gp_npad[gp_id], a, false, (hipStream_t)stream, h->var_trim ? 0 : 1));
     }
     return GPMPC_OK;
 }

@@ -64,6 +64,19 @@ __device__ __forceinline__ double dpp_row_sum(double v) {
     return v;
 }
 
+// sum over the four lanes of a DPP quad (lanes 4i .. 4i + 3), left in each of them
+__device__ __forceinline__ double dpp_quad_sum(double v) {
+    auto mv = [](double x, auto ctrl) {
+        const long long b = __double_as_longlong(x);
+        const int lo = __builtin_amdgcn_update_dpp(0, (int)b, decltype(ctrl)::value, 0xf, 0xf, false);
+        const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), decltype(ctrl)::value, 0xf, 0xf, false);
+        return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+    };
+    v += mv(v, std::integral_constant<int, 0x4E>{});    // quad_perm [2,3,0,1]
+    v += mv(v, std::integral_constant<int, 0xB1>{});    // quad_perm [1,0,3,2]
+    return v;
+}
+
 __host__ __device__ inline int post_ct(int npad) { return npad / 16 < kMaxCT ? npad / 16 : kMaxCT; }
 __host__ __device__ inline int post_stride(int ct) { return 16 * (ct | 1); }
 
@@ -226,10 +239,24 @@ __global__ __launch_bounds__(64 * kPostWaves) void gp_post_kernel(PostBatch pb) 
 // panel loop is unrolled, so the triangle skip costs no branches and the compiler can hoist
 // the B-fragment LDS reads and the next panel's training rows over the MFMAs.  Same math and
 // layout as gp_post_kernel: 8 wavefronts x 16 points, (L^-1)^T panels double-buffered in LDS.
-template <int NT, bool FROM_STATE>
+//
+// NQ > 0: the ragged last column tile on four-column quads.  With nv training rows the last tile
+// holds nr = nv - 16 (NT - 1) real columns and rows; the rest of it is zero in every state a factor
+// can reach (upload, reserve, growth and append write nothing at or past nv; inert blocks leave zero
+// rows and columns).  When nr <= 4 NQ <= 8 the tile's columns go to NQ quads on
+// v_mfma_f64_4x4x4_4b_f64 (love_points has the operand layout: the A operand is the same kernel-value
+// register, the B operand the quad's four columns replicated over the blocks, read from the panel
+// in LDS), acc[NT - 1] does not exist, and the last panel -- rows of the ragged tile, columns of it
+// only -- runs its first NQ K-steps, each against the quads at or right of its rows (the others are
+// zero rows, or the zero triangle of the diagonal tile).  At NT = 13, NQ = 2: 312 full MFMAs and 99
+// quads in place of 364 full MFMAs.  NQ = 0 is the untrimmed kernel.  A variant is exact for every
+// nr <= 4 NQ, so a launch takes the NQ of its largest nr (var_tri_quads).
+template <int NT, bool FROM_STATE, int NQ = 0>
 __global__ __launch_bounds__(64 * kPostWaves) void gp_var_tri_kernel(PostBatch pb) {
     extern __shared__ __attribute__((aligned(16))) double panel[];
     constexpr int W = 16 * (NT | 1);   // odd number of 16-column tiles: conflict-free B fragments
+    constexpr int NF = NQ > 0 ? NT - 1 : NT;               // column tiles on full MFMAs
+    constexpr int NFa = NF > 0 ? NF : 1, NQa = NQ > 0 ? NQ : 1;
     const GPDev& g = pb.g[blockIdx.y];
     const PostArgs& a = pb.a[blockIdx.y];
     if ((int)blockIdx.x * kPostWaves * 16 >= a.P) return;   // uniform
@@ -269,9 +296,12 @@ __global__ __launch_bounds__(64 * kPostWaves) void gp_var_tri_kernel(PostBatch p
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) rw[ks] = rows[16 * q + 4 * ks + kq];
     };
-    f64x4 acc[NT];
+    f64x4 acc[NFa];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int t = 0; t < NFa; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+    double accq[NQa];
+#pragma unroll
+    for (int j = 0; j < NQa; ++j) accq[j] = 0.0;
     fetch(0);
     load_rows(0);
     deposit(0, panel);
@@ -279,11 +309,15 @@ __global__ __launch_bounds__(64 * kPostWaves) void gp_var_tri_kernel(PostBatch p
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
         const double* buf = panel + (q & 1) * 16 * W;
+        // K-steps of the panel: the ragged last one has zero rows from 4 NQ on
+        const int nks = (NQ > 0 && q == NT - 1) ? NQ : 4;   // (q is unrolled: a constant)
         double kv[4];   // k(z_point, x_row) for the four K-steps of the panel (independent exps)
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const double d0 = rw[ks].x - z[0], d1 = rw[ks].y - z[1], d2 = rw[ks].z - z[2];
-            kv[ks] = sf2 * exp_rbf(c * fma(d0, d0, fma(d1, d1, d2 * d2)));
+            if (ks < nks) {
+                const double d0 = rw[ks].x - z[0], d1 = rw[ks].y - z[1], d2 = rw[ks].z - z[2];
+                kv[ks] = sf2 * exp_rbf(c * fma(d0, d0, fma(d1, d1, d2 * d2)));
+            }
         }
         if (q + 1 < NT) {
             fetch(q + 1);
@@ -291,9 +325,18 @@ __global__ __launch_bounds__(64 * kPostWaves) void gp_var_tri_kernel(PostBatch p
         }
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const double* brow = buf + (4 * ks + kq) * W + lc;
+            if (ks < nks) {
+                const double* brow = buf + (4 * ks + kq) * W + lc;
 #pragma unroll
-            for (int t = q; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(kv[ks], brow[16 * t], acc[t], 0, 0, 0);
+                for (int t = q; t < NF; ++t)
+                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(kv[ks], brow[16 * t], acc[t], 0, 0, 0);
+                // quad j of the last tile: lane (kq, lc) holds B[row 4 ks + kq][column 4 j + (lc & 3)]
+                const double* bq = buf + (4 * ks + kq) * W + 16 * (NT - 1) + (lc & 3);
+#pragma unroll
+                for (int j = 0; j < NQ; ++j)
+                    if (q < NT - 1 || j >= ks)   // diagonal tile: columns left of the rows are zero
+                        accq[j] = __builtin_amdgcn_mfma_f64_4x4x4f64(kv[ks], bq[4 * j], accq[j], 0, 0, 0);
+            }
         }
         if (q + 1 < NT) deposit(q + 1, panel + ((q + 1) & 1) * 16 * W);
         __syncthreads();
@@ -301,12 +344,26 @@ __global__ __launch_bounds__(64 * kPostWaves) void gp_var_tri_kernel(PostBatch p
     // acc[t][r] = V[point kq + 4r][column 16 t + lc]
     double sq[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
+    for (int t = 0; t < NF; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) sq[r] = fma(acc[t][r], acc[t][r], sq[r]);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) sq[r] = dpp_row_sum(sq[r]);
-    if (lc == 0) {
+    for (int r = 0; r < 4; ++r) sq[r] = dpp_row_sum(sq[r]);   // (every lane of the row holds the sum)
+    if constexpr (NQ > 0) {
+        // accq[j] (lane 16 m + 4 b + n) = V[point 4 b + m][column 16 (NT - 1) + 4 j + n]: the four lanes
+        // lc >> 2 == r of row kq hold point kq + 4r.  Their squares are added over the four lanes first
+        // and then to the point's full-tile sum, in the same order wherever the point sits in its tile:
+        // masked into sq[r] before the row sum, the association would depend on r, and a point's
+        // variance on its rank in the launch (the overlapped halves are bit-identical to one launch).
+        double tq = 0.0;
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) tq = fma(accq[j], accq[j], tq);
+        tq = dpp_quad_sum(tq);
+        const int r = lc >> 2, pr = p0 + kq + 4 * r;
+        const double s = r == 0 ? sq[0] : r == 1 ? sq[1] : r == 2 ? sq[2] : sq[3];
+        if ((lc & 3) == 0 && pr < a.P)
+            a.var[post_row(a, pr) * a.var_stride + a.var_off] = sf2 - (s + tq) + (a.with_noise ? g.sn2 : 0.0);
+    } else if (lc == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int pr = p0 + kq + 4 * r;
@@ -605,6 +662,39 @@ hipError_t launch_love(const PostBatch& pb, hipStream_t stream) {
     return hipGetLastError();
 }
 
+template <int NT, bool FROM_STATE, int NQ>
+hipError_t launch_var_tri_nq(const PostBatch& pb, int blocks, hipStream_t stream) {
+    static bool attr = false;
+    const int lds = 2 * 16 * 16 * (NT | 1) * (int)sizeof(double);
+    if (!attr) {
+        const hipError_t e = hipFuncSetAttribute((const void*)gp_var_tri_kernel<NT, FROM_STATE, NQ>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+        attr = true;
+    }
+    hipLaunchKernelGGL((gp_var_tri_kernel<NT, FROM_STATE, NQ>), dim3(blocks, pb.n), dim3(64 * kPostWaves), lds, stream, pb);
+    return hipGetLastError();
+}
+
+// Quads for the last column tile of a launch (gp_var_tri_kernel's NQ).  The GPs of a launch share
+// npad but not nv (gpmpc_gp_append moves one GP at a time), and the kernel is one instantiation per
+// launch, so the choice is made here, for the launch, not per blockIdx.y inside the kernel as
+// love_dispatch does: three bodies in one kernel would put the untrimmed body's registers and code
+// on every launch.  A variant with NQ quads is exact for every nr <= 4 NQ, so the launch takes the
+// NQ of its largest nr, and the full tile when that is above 8 columns (or when a caller's npad
+// leaves some GP's last tile empty, nr <= 0: gpmpc_gp_posterior takes any npad >= n).  The choice
+// depends on nv and npad only: both halves of an overlapped step take the same variant.
+static int var_tri_quads(const PostBatch& pb, int ntile) {
+    if (pb.var_full) return 0;
+    int nr = 0;
+    for (int q = 0; q < pb.n; ++q) {
+        const int r = pb.g[q].nv - 16 * (ntile - 1);
+        if (r < 1 || r > 8) return 0;
+        nr = std::max(nr, r);
+    }
+    return (nr + 3) / 4;
+}
+
 template <bool FROM_STATE, int NT = 1>
 hipError_t launch_var_tri(const PostBatch& pb, int ntile, int blocks, int split, hipStream_t stream) {
     if constexpr (NT <= kMaxCT) {
@@ -624,17 +714,11 @@ hipError_t launch_var_tri(const PostBatch& pb, int ntile, int blocks, int split,
                 hipLaunchKernelGGL(k, dim3(sblocks, pb.n), dim3(64 * kPostWaves), lds, stream, pb);
                 return hipGetLastError();
             }
-            static bool attr = false;
-            const int lds = 2 * 16 * 16 * (NT | 1) * (int)sizeof(double);
-            if (!attr) {
-                const hipError_t e = hipFuncSetAttribute((const void*)gp_var_tri_kernel<NT, FROM_STATE>,
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                if (e != hipSuccess) return e;
-                attr = true;
+            switch (var_tri_quads(pb, NT)) {
+                case 1: return launch_var_tri_nq<NT, FROM_STATE, 1>(pb, blocks, stream);
+                case 2: return launch_var_tri_nq<NT, FROM_STATE, 2>(pb, blocks, stream);
+                default: return launch_var_tri_nq<NT, FROM_STATE, 0>(pb, blocks, stream);
             }
-            hipLaunchKernelGGL((gp_var_tri_kernel<NT, FROM_STATE>), dim3(blocks, pb.n), dim3(64 * kPostWaves), lds,
-                               stream, pb);
-            return hipGetLastError();
         }
         return launch_var_tri<FROM_STATE, NT + 1>(pb, ntile, blocks, split, stream);
     }
@@ -708,8 +792,10 @@ hipError_t launch_gp_post_batch(const PostBatch& pb, bool from_state, hipStream_
     return hipGetLastError();
 }
 
-hipError_t launch_gp_post(const GPDev& g, int npad, const PostArgs& a, bool from_state, hipStream_t stream) {
+hipError_t launch_gp_post(const GPDev& g, int npad, const PostArgs& a, bool from_state, hipStream_t stream,
+                          int var_full) {
     PostBatch pb{};
+    pb.var_full = var_full;
     pb.g[0] = g;
     pb.a[0] = a;
     pb.npad[0] = npad;

@@ -264,6 +264,9 @@ struct PostBatch {
     int32_t step_points;
     // triangular variance kernel's column split (GPMPC_TUNE_VAR_SPLIT): 0 automatic, 1 or 4 forced
     int32_t var_split;
+    // 1: the triangular variance kernel multiplies its ragged last column tile in full
+    // (GPMPC_TUNE_VAR_TRIM = 0); 0: on four-column quads where at most 8 of its columns are real
+    int32_t var_full;
 };
 
 // One block of m <= 16 rows appended to an exact GP (gp_append.hip; gpmpc_gp_append fills it per block).
@@ -307,7 +310,8 @@ int model_unc_dims(int model, int32_t* unc);   // the model's uncertain state di
 hipError_t launch_stage_cost(const ProblemDev& P, const double* x, const double* u, const int32_t* tstep,
                              const int32_t* status, double* cost, int B, hipStream_t stream);
 hipError_t launch_gp_mean_grad(const GPDev& g, const double* Z, int P, double* mean, double* grad, hipStream_t stream);
-hipError_t launch_gp_post(const GPDev& g, int npad, const PostArgs& a, bool from_state, hipStream_t stream);
+hipError_t launch_gp_post(const GPDev& g, int npad, const PostArgs& a, bool from_state, hipStream_t stream,
+                          int var_full = 0);   // PostBatch::var_full
 hipError_t launch_gp_post_batch(const PostBatch& pb, bool from_state, hipStream_t stream);
 hipError_t launch_plant(int model, const double* params, double dt, const double* x, const double* u, double* xn,
                         int32_t* tstep, int B, hipStream_t stream);

@@ -274,7 +274,8 @@ class BatchSolver:
 
     def set_tuning(self, **opts):
         """Performance switches (gpmpc_set_tuning): lin_cache=0/1, order=0/1/2, overlap=0/1,
-        var_split=0/1/4, event_fence=0/1, seg=0/1, tail=K, seg_pivot=k.  Outputs do not depend on them (A/B knobs).
+        var_split=0/1/4, event_fence=0/1, seg=0/1, tail=K, seg_pivot=k, var_trim=0/1.  Outputs do not depend on them (A/B knobs;
+        var_trim: the tightening variances agree to rounding).
 
         shift=0/1 is the exception.  With 1, an instance whose previous solve ended with status 0 or 2
         and whose ``tstep`` has advanced by exactly one (modulo the reference length) starts its SQP

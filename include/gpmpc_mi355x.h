@@ -282,7 +282,13 @@ gpmpc_status gpmpc_get_launch_segments(gpmpc_handle* h, int32_t batch, int32_t* 
  *                          unshifted one to the solver tolerance and the iteration path (sqp_iter,
  *                          qp_iter, a status-2 iterate) differs.  A shifted solve recomputes its
  *                          first linearisation (the cache holds no row for the duplicated last
- *                          stage).  Any other value: GPMPC_ERR_ARG */
+ *                          stage).  Any other value: GPMPC_ERR_ARG
+ *   GPMPC_TUNE_VAR_TRIM    1 (default): the one-wave triangular variance kernel (N <= 256) carries a
+ *                          last 16-column tile with at most 8 real columns (N mod 16 in 1..8 for
+ *                          every GP of the launch) on one or two four-column MFMA quads and skips
+ *                          that tile's zero rows; 0: the whole padded tile is multiplied.  The
+ *                          skipped products are exact zeros; the variances agree to rounding (the
+ *                          order of additions differs) */
 enum {
     GPMPC_TUNE_LIN_CACHE = 0,
     GPMPC_TUNE_ORDER = 1,
@@ -292,7 +298,8 @@ enum {
     GPMPC_TUNE_SEG = 5,
     GPMPC_TUNE_TAIL = 6,
     GPMPC_TUNE_SEG_PIVOT = 7,
-    GPMPC_TUNE_SHIFT = 8
+    GPMPC_TUNE_SHIFT = 8,
+    GPMPC_TUNE_VAR_TRIM = 9
 };
 gpmpc_status gpmpc_set_tuning(gpmpc_handle* h, int32_t option, int32_t value);
 
