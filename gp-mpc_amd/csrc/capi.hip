@@ -95,6 +95,7 @@ struct gpmpc_handle {
     bool gp_exact[kMaxGP] = {false, false, false, false};
     double* gp_linvT_alt[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
     double* gp_app[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
+    double* gp_drp[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};   // gpmpc_gp_drop_oldest's scratch and staging
     double* gp_vroot[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};   // LOVE roots (tightening only)
     int gp_vroot_cols[kMaxGP] = {0, 0, 0, 0};
     int gp_vroot_rank[kMaxGP] = {0, 0, 0, 0};
@@ -252,6 +253,7 @@ static void free_handle(gpmpc_handle* h) {
         if (h->gp_vroot[g]) (void)hipFree(h->gp_vroot[g]);
         if (h->gp_linvT_alt[g]) (void)hipFree(h->gp_linvT_alt[g]);
         if (h->gp_app[g]) (void)hipFree(h->gp_app[g]);
+        if (h->gp_drp[g]) (void)hipFree(h->gp_drp[g]);
     }
     delete h;
 }
@@ -472,7 +474,7 @@ gpmpc_status gpmpc_set_gp(gpmpc_handle* h, int32_t gp_id, int32_t n, int32_t d, 
     }
     for (double** p : {&h->gp_rows[gp_id], &h->gp_vrows[gp_id], &h->gp_linvT[gp_id], &h->gp_tiles[gp_id],
                        &h->gp_vroot[gp_id], &h->gp_linvT_alt[gp_id],
-                       &h->gp_app[gp_id]}) {   // (a LOVE root belongs to the previous training set)
+                       &h->gp_app[gp_id], &h->gp_drp[gp_id]}) {   // (a LOVE root belongs to the previous training set)
         if (*p) HIPCHK(hipFree(*p));
         *p = nullptr;
     }
@@ -518,6 +520,10 @@ gpmpc_status gpmpc_set_gp(gpmpc_handle* h, int32_t gp_id, int32_t n, int32_t d, 
 // Scratch of the append kernels for a capacity of cpad rows (GPAppend): W^T [16][cpad] | per-tile
 // means [cpad/16][16] | L_b^-1 [256] | beta [16] | status word
 static size_t app_scratch_doubles(int cpad) { return (size_t)16 * cpad + cpad + 256 + 16 + 1; }
+// Scratch and staging of the drop kernels for a capacity of cpad rows (GPDrop): V^T [16][cpad] | M21 g
+// [cpad] | E_T [cpad/16][256] | D_T [cpad/16][256] | staged rows [cpad][4] | tX [cpad/16][64] | tW
+// [cpad/16][64] | status word
+static size_t drop_scratch_doubles(int cpad) { return (size_t)(16 + 1 + 16 + 16 + 4 + 4 + 4) * cpad + 1; }
 
 gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) {
     if (!h) return fail(GPMPC_ERR_ARG, "null handle");
@@ -533,9 +539,9 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
     const size_t npad = h->gp_npad[gp_id], nt = g.ntile;
     const bool lin = h->gp_linvT[gp_id] != nullptr;
     // everything is allocated and filled before the handle changes
-    double *rows = nullptr, *tiles = nullptr, *la = nullptr, *lb = nullptr, *app = nullptr;
+    double *rows = nullptr, *tiles = nullptr, *la = nullptr, *lb = nullptr, *app = nullptr, *drp = nullptr;
     auto drop = [&]() {
-        for (double* p : {rows, tiles, la, lb, app})
+        for (double* p : {rows, tiles, la, lb, app, drp})
             if (p) (void)hipFree(p);
     };
     hipError_t e = hipMalloc(&rows, cpad * 4 * sizeof(double));
@@ -543,6 +549,7 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
     if (e == hipSuccess && lin) e = hipMalloc(&la, cpad * cpad * sizeof(double));
     if (e == hipSuccess && lin) e = hipMalloc(&lb, cpad * cpad * sizeof(double));
     if (e == hipSuccess && lin) e = hipMalloc(&app, app_scratch_doubles((int)cpad) * sizeof(double));
+    if (e == hipSuccess && lin) e = hipMalloc(&drp, drop_scratch_doubles((int)cpad) * sizeof(double));
     if (e != hipSuccess) {
         drop();
         return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
@@ -553,6 +560,7 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
     if (e == hipSuccess) e = hipMemcpy(tiles, g.tX, nt * 64 * sizeof(double), hipMemcpyDeviceToDevice);
     if (e == hipSuccess) e = hipMemcpy(tiles + ct * 64, g.tW, nt * 64 * sizeof(double), hipMemcpyDeviceToDevice);
     if (e == hipSuccess && lin) e = hipMemset(app, 0, app_scratch_doubles((int)cpad) * sizeof(double));
+    if (e == hipSuccess && lin) e = hipMemset(drp, 0, drop_scratch_doubles((int)cpad) * sizeof(double));
     // the factor keeps its stride npad (the variance kernels' layout) at the head of the first buffer
     if (e == hipSuccess && lin)
         e = hipMemcpy(la, h->gp_linvT[gp_id], npad * npad * sizeof(double), hipMemcpyDeviceToDevice);
@@ -562,7 +570,7 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
         return fail(GPMPC_ERR_HIP, std::string("gpmpc_gp_reserve: ") + hipGetErrorString(e));
     }
     for (double** p : {&h->gp_rows[gp_id], &h->gp_tiles[gp_id], &h->gp_linvT[gp_id], &h->gp_linvT_alt[gp_id],
-                       &h->gp_app[gp_id]}) {
+                       &h->gp_app[gp_id], &h->gp_drp[gp_id]}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -571,6 +579,7 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
     h->gp_linvT[gp_id] = la;
     h->gp_linvT_alt[gp_id] = lb;
     h->gp_app[gp_id] = app;
+    h->gp_drp[gp_id] = drp;
     g.rows = g.vrows = rows;
     g.linvT = la;
     g.tX = tiles;
@@ -652,6 +661,79 @@ gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const do
         // the row count advances whether the block is accepted or written as inert rows
         g.n = g.nv = n0 + mb;
         g.ntile = (g.n + 15) / 16;
+    }
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int32_t* ok_dev, void* stream) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
+    if (!h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
+    if (!h->gp_exact[gp_id]) return fail(GPMPC_ERR_STATE, "FITC upload (Xv != X): only an exact GP drops rows");
+    if (!h->gp_linvT[gp_id]) return fail(GPMPC_ERR_STATE, "drop needs Linv (the GP was set without it)");
+    if (h->gp_vroot[gp_id])
+        return fail(GPMPC_ERR_STATE, "a LOVE root is installed: it belongs to the old training set (drop it first, "
+                                     "gpmpc_set_gp_variance_root with R = NULL)");
+    if (!h->gp_drp[gp_id] || !h->gp_linvT_alt[gp_id])
+        return fail(GPMPC_ERR_STATE, "drop needs the second factor buffer (gpmpc_gp_reserve first)");
+    GPDev& g = h->P.gp[gp_id];
+    if (m < 1) return fail(GPMPC_ERR_ARG, "no rows to drop");
+    if (m >= g.n)
+        return fail(GPMPC_ERR_ARG, "at least one row stays: " + std::to_string(m) + " of " + std::to_string(g.n) +
+                                       " rows asked for");
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const int cpad = (h->gp_cap[gp_id] + 15) / 16 * 16, ct = cpad / 16, d = h->md.gp_dim[gp_id];
+    double* rows = h->gp_rows[gp_id];
+    double* tX = h->gp_tiles[gp_id];
+    double* tW = h->gp_tiles[gp_id] + (size_t)ct * 64;
+    double* drp = h->gp_drp[gp_id];
+    for (int done = 0, blk = 0; done < m; done += 16, ++blk) {
+        const int mb = std::min(16, m - done);
+        const int n0 = g.n, npad0 = h->gp_npad[gp_id], n1 = n0 - mb, npad1 = (n1 + 15) / 16 * 16;
+        // the model changes with the first launch queued: the cache must not serve its old rows
+        bump_lin(h);
+        GPDrop a{};
+        a.src = h->gp_linvT[gp_id];
+        a.dst = h->gp_linvT_alt[gp_id];
+        a.rows = rows;
+        a.tX = tX;
+        a.npad0 = npad0;
+        a.npad1 = npad1;
+        a.n0 = n0;
+        a.m = mb;
+        a.d = d;
+        for (int k = 0; k < 3; ++k) a.xbar[k] = g.xbar[k];
+        a.vt = drp;
+        a.ldv = cpad;
+        a.w = a.vt + (size_t)16 * cpad;
+        a.et = a.w + cpad;
+        a.dt = a.et + (size_t)ct * 256;
+        a.srows = a.dt + (size_t)ct * 256;
+        a.stX = a.srows + (size_t)cpad * 4;
+        a.stW = a.stX + (size_t)ct * 64;
+        a.flag = reinterpret_cast<int32_t*>(a.stW + (size_t)ct * 64);
+        a.ok = ok_dev ? ok_dev + blk : nullptr;
+        HIPCHK(launch_gp_drop(a, s));
+        // the staged rows and tile pack replace the live ones (disjoint buffers); what lies between the
+        // new and the old padded size becomes what rows past n always are: zero
+        const size_t rb = (size_t)npad1 * 4 * sizeof(double), rb0 = (size_t)npad0 * 4 * sizeof(double);
+        HIPCHK(hipMemcpyAsync(rows, a.srows, rb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(tX, a.stX, rb, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(tW, a.stW, rb, hipMemcpyDeviceToDevice, s));
+        if (npad1 < npad0) {
+            HIPCHK(hipMemsetAsync(rows + (size_t)npad1 * 4, 0, rb0 - rb, s));
+            HIPCHK(hipMemsetAsync(tX + (size_t)npad1 * 4, 0, rb0 - rb, s));
+            HIPCHK(hipMemsetAsync(tW + (size_t)npad1 * 4, 0, rb0 - rb, s));
+        }
+        // the two factor buffers swap roles
+        std::swap(h->gp_linvT[gp_id], h->gp_linvT_alt[gp_id]);
+        g.linvT = h->gp_linvT[gp_id];
+        h->gp_npad[gp_id] = npad1;
+        g.n = g.nv = n1;
+        g.ntile = (n1 + 15) / 16;
     }
     return GPMPC_OK;
 }

@@ -294,8 +294,37 @@ struct GPAppend {
     int32_t* accepted;    // the caller's status word of this block, may be null
 };
 
-// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip).
+// One block of m <= 16 oldest rows dropped from an exact GP (gp_drop.hip; gpmpc_gp_drop_oldest fills it
+// per block).  The factor moves from src to dst (the GP's two factor buffers); rows / tX / tW are read
+// in place and their shifted successors written to a staging region the caller copies back.
+struct GPDrop {
+    const double* src;    // [npad0][npad0], the factor before the block
+    double* dst;          // [npad1][npad1], the factor after it: written in full, zeros included
+    const double* rows;   // GPDev::rows / tX before the block
+    const double* tX;
+    double* srows;        // staging: rows [npad1][4], tX [npad1/16][64], tW [npad1/16][64]
+    double* stX;
+    double* stW;
+    int32_t npad0;        // n0 rounded up to 16
+    int32_t npad1;        // n0 - m rounded up to 16
+    int32_t n0;           // rows before the block
+    int32_t m;            // rows dropped (m < n0)
+    int32_t d;
+    double xbar[3];       // the tile pack's centre (unchanged by drops)
+    // scratch of the GP: V^T [16][ldv], M21 g [ldv], E_T and D_T [npad1/16][16][16] each, the block's
+    // status (1: every pivot finite and positive)
+    double* vt;
+    int32_t ldv;
+    double* w;
+    double* et;
+    double* dt;
+    int32_t* flag;
+    int32_t* ok;          // the caller's status word of this block, may be null
+};
+
+// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip).
 hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream);
+hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream);
 // count < 0: the whole batch; else ranks first .. first + count - 1 of order[] (launch_sqp_order)
 hipError_t launch_sqp(const ProblemDev& P, const StateDev& S, const StepIO& io, int batch, hipStream_t stream,
                       int first = 0, int count = -1);

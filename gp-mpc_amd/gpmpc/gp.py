@@ -107,6 +107,19 @@ class GaussianProcess:
         self.K, self.K_inv, self._dev = None, None, None
         return self
 
+    def drop_oldest(self, m: int):
+        """Remove the first m training rows (1 <= m < n), hyperparameters unchanged: the mirror of
+        ``append_data`` for a sliding window.  The cached covariances and device layout are dropped
+        (the solver handle's copy is shortened by ``BatchSolver.drop_gp``)."""
+        m = int(m)
+        if not 1 <= m < self.n_ind_points:
+            raise ValueError(f"drop_oldest: m must be 1..{self.n_ind_points - 1} (at least one row stays), got {m}")
+        self.train_inputs = (self.train_inputs[0][m:].clone(),)
+        self.train_targets = self.train_targets[m:].clone()
+        self.n_ind_points = self.train_inputs[0].shape[0]
+        self.K, self.K_inv, self._dev = None, None, None
+        return self
+
     def parameters(self):
         return [self.raw_lengthscale, self.raw_outputscale, self.raw_noise]
 

@@ -187,14 +187,38 @@ class GPMPC:
         self.gaussian_process = gps
         self._requires_recompile = True
 
-    def append_data(self, inputs: np.ndarray, targets: np.ndarray) -> list[torch.Tensor]:
+    def drop_oldest(self, m: int) -> list[torch.Tensor]:
+        """Remove the ``m`` oldest training rows of every GP on the solver handle, on the device
+        (``BatchSolver.drop_gp``, queued on the current stream, no refactorisation), and of the Python
+        GP objects with them (``GaussianProcess.drop_oldest``).  At least one row stays.  Returns the
+        status flags per GP (device tensors; a 0 means that GP must be uploaded again).  Not
+        available in sparse (FITC) mode, like ``append_data``."""
+        if self.sparse:
+            raise _lib.GPMPCError("drop_oldest: not available in sparse (FITC) mode")
+        assert self.gaussian_process is not None and not self._requires_recompile, \
+            "GP model must be uploaded (call reset())"
+        m = int(m)
+        n = self.solver.gp_size(0)[0]
+        if not 1 <= m < n:   # before any GP changes, so the handle's GPs stay in step
+            raise ValueError(f"drop_oldest: m must be 1..{n - 1} (at least one row stays), got {m}")
+        flags = []
+        for i in range(len(self.gp_idx)):
+            flags.append(self.solver.drop_gp(i, m))
+            self.gaussian_process[i].drop_oldest(m)
+        return flags
+
+    def append_data(self, inputs: np.ndarray, targets: np.ndarray, evict_oldest: bool = False) -> list[torch.Tensor]:
         """Fold new observations into the uploaded GPs between two control steps, hyperparameters
         unchanged: ``inputs`` (m, sum d_g) and ``targets`` (m, n_gp) in GP-input space, as
         ``preprocess_data`` returns them.  Every GP on the solver handle is extended on the device
         (``BatchSolver.append_gp``, queued on the current stream) and the Python GP objects with it
         (``GaussianProcess.append_data``), so a later ``train_gp`` refit or upload sees all data.
         Returns the accepted flags per GP (device tensors).  Needs room (``gp_capacity``); not
-        available in sparse (FITC) mode, whose inducing weights belong to the old training set."""
+        available in sparse (FITC) mode, whose inducing weights belong to the old training set.
+
+        ``evict_oldest=True`` makes the training set a sliding window: when the new rows would
+        exceed the capacity, exactly the excess is dropped from the old end first
+        (``drop_oldest``).  Appending more rows than the capacity holds stays an error."""
         if self.sparse:
             raise _lib.GPMPCError("append_data: not available in sparse (FITC) mode")
         assert self.gaussian_process is not None and not self._requires_recompile, \
@@ -204,9 +228,13 @@ class GPMPC:
         if inputs.shape[1] != sum(self.model.gp_dims) or targets.shape != (inputs.shape[0], self.model.n_gp):
             raise ValueError(f"expected inputs (m, {sum(self.model.gp_dims)}) and targets (m, {self.model.n_gp})")
         n, cap = self.solver.gp_size(0)
-        if n + inputs.shape[0] > cap:   # before any GP changes, so the handle's GPs stay in step
+        excess = n + inputs.shape[0] - cap
+        # before any GP changes, so the handle's GPs stay in step (an eviction leaves at least one old row)
+        if excess > 0 and (not evict_oldest or excess >= n):
             raise _lib.GPMPCError(f"append_data: capacity exceeded ({n} + {inputs.shape[0]} rows, capacity {cap}; "
                                   "construct GPMPC with gp_capacity)")
+        if excess > 0:
+            self.drop_oldest(excess)
         flags = []
         for i, idx in enumerate(self.gp_idx):
             X = torch.tensor(inputs[:, idx], device=self.device)

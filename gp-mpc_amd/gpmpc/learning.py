@@ -59,13 +59,19 @@ def run_evaluation(ctrl, x0: np.ndarray, steps: int, tstep0: np.ndarray | None =
 
 
 def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, seed: int,
-                       tstep0: np.ndarray | None = None) -> dict:
+                       tstep0: np.ndarray | None = None, sliding: bool = False) -> dict:
     """A closed-loop episode that learns while it runs: after every plant step a seeded random
     choice of ``append_per_step`` of the step's B transitions is preprocessed
     (``GPMPC.preprocess_data``) and appended to the uploaded GPs (``GPMPC.append_data``, a
     bordered Cholesky update on the device), until the GPs' capacity (``gp_capacity``) is reached;
-    the next control step runs on the extended model.  Hyperparameters stay as trained.  Returns
-    the dict of :func:`run_evaluation` plus ``n_train`` (steps,), the training rows after each step."""
+    the next control step runs on the extended model.  Hyperparameters stay as trained.
+
+    ``sliding=True`` keeps learning past the capacity: every step still appends
+    ``append_per_step`` rows, the oldest rows making room for them on the device
+    (``append_data(evict_oldest=True)``), so the training set is a moving window of fixed size.
+
+    Returns the dict of :func:`run_evaluation` plus ``n_train`` (steps,), the training rows after
+    each step."""
     ctrl.reset()
     solver = ctrl.solver
     dev = solver.device
@@ -85,11 +91,13 @@ def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, s
         obs = solver.plant_step(obs, u, ts)   # advances the reference index too
         data["obs"].append(obs.cpu().numpy())
         n, cap = solver.gp_size(0)
-        pick = rng.choice(B, min(append_per_step, B), replace=False)[:max(cap - n, 0)]
+        pick = rng.choice(B, min(append_per_step, B), replace=False)
+        if not sliding:
+            pick = pick[:max(cap - n, 0)]
         if len(pick):
             inputs, targets = ctrl.preprocess_data(data["obs"][-2][pick], data["action"][-1][pick],
                                                    data["obs"][-1][pick])
-            ctrl.append_data(inputs, targets)
+            ctrl.append_data(inputs, targets, evict_oldest=sliding)
         data["n_train"].append(solver.gp_size(0)[0])
     return {k: np.array(v) for k, v in data.items()}
 

@@ -193,6 +193,19 @@ class BatchSolver:
                                             self._stream()))
         return flags
 
+    def drop_gp(self, gp_id: int, m: int) -> torch.Tensor:
+        """Remove the ``m`` oldest training rows of the handle's GP ``gp_id`` on the current stream
+        (gpmpc_gp_drop_oldest): one update of the inverse factor and the weights per block of up to
+        16 rows, hyperparameters unchanged, no refactorisation and no synchronisation of its own; row
+        ``j + m`` becomes row ``j`` and the capacity stays.  Needs ``reserve_gp`` and leaves at least
+        one row.  Returns the status flags, a device int32 tensor with one entry per block (1: every
+        pivot was finite and positive; 0: the GP's contents are unspecified, upload it again).  The
+        Python GP objects are not touched (``GaussianProcess.drop_oldest``)."""
+        m = int(m)
+        flags = torch.empty(max((m + 15) // 16, 1), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gpmpc_gp_drop_oldest(self._h, int(gp_id), m, flags.data_ptr(), self._stream()))
+        return flags
+
     def gp_size(self, gp_id: int) -> tuple[int, int]:
         """(training rows, capacity) of the handle's GP ``gp_id`` (gpmpc_gp_size)."""
         n, cap = ctypes.c_int32(), ctypes.c_int32()

@@ -124,6 +124,24 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity);
 gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const double* Xnew_dev,
                              const double* ynew_dev, int32_t* accepted_dev, void* stream);
 
+/* Remove the m oldest training rows (rows 0 .. m-1; row j + m becomes row j) of GP gp_id on
+ * `stream`, the counterpart of gpmpc_gp_append for a bounded, moving training set (the reference
+ * only ever grows its data set, stacking each epoch's samples onto it before a refit,
+ * scripts/run_gp_mpc.py:115-120; here "drop m, append m" keeps the size fixed while the loop runs).  Blocks of up to 16 rows, each one
+ * rank-m update of (L^-1)^T and of alpha = K^-1 y with no stored targets (csrc/gp_drop.hip): no
+ * refactorisation, no host synchronisation, nothing read back; hyperparameters, xbar and the
+ * capacity are unchanged, gpmpc_gp_size reports the new count.  Inert rows (rejected append
+ * blocks) may be among the dropped and the kept rows; kept ones stay inert.
+ * ok_dev: device int32 [ceil(m/16)], may be NULL; 1 when every pivot of the block's update was
+ * finite and positive, else 0.  After a 0 the contents of the GP are unspecified (nothing is
+ * accessed out of bounds, but means and variances are meaningless): upload it again with
+ * gpmpc_set_gp before it is used.
+ * Refused, with the GP unchanged: m < 1 or m >= n, at least one row stays (GPMPC_ERR_ARG); GP not
+ * set, set without Linv, a FITC upload (Xv != X), a LOVE root installed (drop it first with
+ * gpmpc_set_gp_variance_root(R = NULL)), or no gpmpc_gp_reserve since gpmpc_set_gp -- the update
+ * writes the factor into the second buffer a reserve allocates (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int32_t* ok_dev, void* stream);
+
 /* Training rows of GP gp_id (inert rows included) and its capacity; either may be NULL. */
 gpmpc_status gpmpc_gp_size(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* capacity);
 
