@@ -13,6 +13,11 @@ constexpr int kMaxH = 63;       // one lane per stage 0..H (64-lane wavefront)
 constexpr int kPhases = 15;  // diagnostic phase slots (GPMPC_TIMING builds; sqp_kernel.hip TPHASE)
 constexpr int kMaxParams = 16;
 constexpr int kStatsSlots = 12;  // per-instance solver statistics (gpmpc_set_stats_buffer, = GPMPC_STATS_SLOTS)
+// Floor of the IPM's slacks after a step (HPIPM's t_min; oracle/cpu_ref.cpp has the same).  With a
+// bound active, the 0.995 steps can take a slack to 1e-14 while the other QP residuals are still above
+// a 1e-11 tolerance; Sigma = lam / s then passes 1e12, the Riccati recursion cancels every digit of the
+// cost-to-go, Huu loses definiteness and a feasible QP ends as status 4.
+constexpr double kSlackMin = 1e-12;
 
 enum ModelId : int32_t { kQuad2D = 0, kQuad3D = 1, kCartpole = 2 };
 

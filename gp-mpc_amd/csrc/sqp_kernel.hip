@@ -2985,8 +2985,8 @@ struct SqpKernel {
                 for (int j = 0; j < NV; ++j) {
                     if (avq(j)) {
                         d[j] = fma(alpha, dd[j], d[j]);
-                        sl[j] = fma(alpha, dsl[j], sl[j]);
-                        su[j] = fma(alpha, dsu[j], su[j]);
+                        sl[j] = fmax(fma(alpha, dsl[j], sl[j]), kSlackMin);
+                        su[j] = fmax(fma(alpha, dsu[j], su[j]), kSlackMin);
                         ll[j] = fma(alpha, dll[j], ll[j]);
                         lu[j] = fma(alpha, dlu[j], lu[j]);
                     }

@@ -35,6 +35,7 @@ namespace {
 constexpr int MX = 12, MU = 4, MB = MX + MU, MG = 4;
 enum { kQuad2D = 0, kQuad3D = 1, kCartpole = 2 };
 enum { kSuccess = 0, kNaN = 1, kMaxIter = 2, kQPFailure = 4 };
+constexpr double kSlackMin = 1e-12;   // floor of the IPM's slacks after a step (Instance::qp)
 
 struct GP {
     int n = 0, d = 0, nv = 0;
@@ -518,6 +519,13 @@ struct Instance {
             const double a = std::min(1.0, 0.995 * step_len());
             for (int i = 0; i < n; ++i) {
                 d[i] += a * dd[i]; sl[i] += a * dsl[i]; su[i] += a * dsu[i]; l1[i] += a * dll[i]; l2[i] += a * dlu[i];
+                // slack floor (HPIPM's t_min; the kernel's kSlackMin): with a bound active, the 0.995 steps
+                // can take a slack to 1e-14 while the other residuals are still above a 1e-11 tolerance;
+                // Sigma = lam / s then passes 1e12 and the Riccati recursion P = Q + A'PA - Hux' Huu^-1 Hux
+                // cancels every digit of the cost-to-go, which loses definiteness (Huu pivot < 0).  The
+                // floor is below any tolerance in use and enters the slack residuals like any other step.
+                sl[i] = std::max(sl[i], kSlackMin);
+                su[i] = std::max(su[i], kSlackMin);
             }
             for (int i = 0; i < m; ++i) pq[i] += a * dp[i];
             for (int i = 0; i < n; ++i)
