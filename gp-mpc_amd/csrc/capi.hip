@@ -96,6 +96,7 @@ struct gpmpc_handle {
     double* gp_linvT_alt[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
     double* gp_app[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
     double* gp_drp[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};   // gpmpc_gp_drop_oldest's scratch and staging
+    double* gp_rfc[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};   // gpmpc_gp_refactor's scratch
     double* gp_vroot[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};   // LOVE roots (tightening only)
     int gp_vroot_cols[kMaxGP] = {0, 0, 0, 0};
     int gp_vroot_rank[kMaxGP] = {0, 0, 0, 0};
@@ -254,6 +255,7 @@ static void free_handle(gpmpc_handle* h) {
         if (h->gp_linvT_alt[g]) (void)hipFree(h->gp_linvT_alt[g]);
         if (h->gp_app[g]) (void)hipFree(h->gp_app[g]);
         if (h->gp_drp[g]) (void)hipFree(h->gp_drp[g]);
+        if (h->gp_rfc[g]) (void)hipFree(h->gp_rfc[g]);
     }
     delete h;
 }
@@ -474,7 +476,7 @@ gpmpc_status gpmpc_set_gp(gpmpc_handle* h, int32_t gp_id, int32_t n, int32_t d, 
     }
     for (double** p : {&h->gp_rows[gp_id], &h->gp_vrows[gp_id], &h->gp_linvT[gp_id], &h->gp_tiles[gp_id],
                        &h->gp_vroot[gp_id], &h->gp_linvT_alt[gp_id],
-                       &h->gp_app[gp_id], &h->gp_drp[gp_id]}) {   // (a LOVE root belongs to the previous training set)
+                       &h->gp_app[gp_id], &h->gp_drp[gp_id], &h->gp_rfc[gp_id]}) {   // (a LOVE root belongs to the previous training set)
         if (*p) HIPCHK(hipFree(*p));
         *p = nullptr;
     }
@@ -524,6 +526,9 @@ static size_t app_scratch_doubles(int cpad) { return (size_t)16 * cpad + cpad + 
 // [cpad] | E_T [cpad/16][256] | D_T [cpad/16][256] | staged rows [cpad][4] | tX [cpad/16][64] | tW
 // [cpad/16][64] | status word
 static size_t drop_scratch_doubles(int cpad) { return (size_t)(16 + 1 + 16 + 16 + 4 + 4 + 4) * cpad + 1; }
+// Scratch of the refactorisation for a capacity of cpad rows (GPRefactor): L_kk^-1 [cpad/16][256] | w [cpad] |
+// masked targets [cpad] | the inert mask [cpad] int32 (in cpad/2 doubles) | status word
+static size_t refactor_scratch_doubles(int cpad) { return (size_t)(16 + 2) * cpad + cpad / 2 + 1; }
 
 gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) {
     if (!h) return fail(GPMPC_ERR_ARG, "null handle");
@@ -539,9 +544,9 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
     const size_t npad = h->gp_npad[gp_id], nt = g.ntile;
     const bool lin = h->gp_linvT[gp_id] != nullptr;
     // everything is allocated and filled before the handle changes
-    double *rows = nullptr, *tiles = nullptr, *la = nullptr, *lb = nullptr, *app = nullptr, *drp = nullptr;
+    double *rows = nullptr, *tiles = nullptr, *la = nullptr, *lb = nullptr, *app = nullptr, *drp = nullptr, *rfc = nullptr;
     auto drop = [&]() {
-        for (double* p : {rows, tiles, la, lb, app, drp})
+        for (double* p : {rows, tiles, la, lb, app, drp, rfc})
             if (p) (void)hipFree(p);
     };
     hipError_t e = hipMalloc(&rows, cpad * 4 * sizeof(double));
@@ -550,6 +555,7 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
     if (e == hipSuccess && lin) e = hipMalloc(&lb, cpad * cpad * sizeof(double));
     if (e == hipSuccess && lin) e = hipMalloc(&app, app_scratch_doubles((int)cpad) * sizeof(double));
     if (e == hipSuccess && lin) e = hipMalloc(&drp, drop_scratch_doubles((int)cpad) * sizeof(double));
+    if (e == hipSuccess && lin) e = hipMalloc(&rfc, refactor_scratch_doubles((int)cpad) * sizeof(double));
     if (e != hipSuccess) {
         drop();
         return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
@@ -561,6 +567,7 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
     if (e == hipSuccess) e = hipMemcpy(tiles + ct * 64, g.tW, nt * 64 * sizeof(double), hipMemcpyDeviceToDevice);
     if (e == hipSuccess && lin) e = hipMemset(app, 0, app_scratch_doubles((int)cpad) * sizeof(double));
     if (e == hipSuccess && lin) e = hipMemset(drp, 0, drop_scratch_doubles((int)cpad) * sizeof(double));
+    if (e == hipSuccess && lin) e = hipMemset(rfc, 0, refactor_scratch_doubles((int)cpad) * sizeof(double));
     // the factor keeps its stride npad (the variance kernels' layout) at the head of the first buffer
     if (e == hipSuccess && lin)
         e = hipMemcpy(la, h->gp_linvT[gp_id], npad * npad * sizeof(double), hipMemcpyDeviceToDevice);
@@ -570,7 +577,7 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
         return fail(GPMPC_ERR_HIP, std::string("gpmpc_gp_reserve: ") + hipGetErrorString(e));
     }
     for (double** p : {&h->gp_rows[gp_id], &h->gp_tiles[gp_id], &h->gp_linvT[gp_id], &h->gp_linvT_alt[gp_id],
-                       &h->gp_app[gp_id], &h->gp_drp[gp_id]}) {
+                       &h->gp_app[gp_id], &h->gp_drp[gp_id], &h->gp_rfc[gp_id]}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -580,6 +587,7 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
     h->gp_linvT_alt[gp_id] = lb;
     h->gp_app[gp_id] = app;
     h->gp_drp[gp_id] = drp;
+    h->gp_rfc[gp_id] = rfc;
     g.rows = g.vrows = rows;
     g.linvT = la;
     g.tX = tiles;
@@ -735,6 +743,58 @@ gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int
         g.n = g.nv = n1;
         g.ntile = (n1 + 15) / 16;
     }
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_refactor(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double lengthscale,
+                               double outputscale, double noise, int32_t* ok_dev, void* stream) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
+    if (!y_dev) return fail(GPMPC_ERR_ARG, "no targets");
+    if (!(std::isfinite(lengthscale) && lengthscale > 0.0) || !(std::isfinite(outputscale) && outputscale > 0.0) ||
+        !(std::isfinite(noise) && noise > 0.0))
+        return fail(GPMPC_ERR_ARG, "hyperparameters must be finite and positive");
+    if (!h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
+    if (!h->gp_exact[gp_id]) return fail(GPMPC_ERR_STATE, "FITC upload (Xv != X): only an exact GP is refactorised");
+    if (!h->gp_linvT[gp_id]) return fail(GPMPC_ERR_STATE, "refactor needs Linv (the GP was set without it)");
+    if (h->gp_vroot[gp_id])
+        return fail(GPMPC_ERR_STATE, "a LOVE root is installed: it belongs to the old factor (drop it first, "
+                                     "gpmpc_set_gp_variance_root with R = NULL)");
+    if (!h->gp_rfc[gp_id] || !h->gp_linvT_alt[gp_id])
+        return fail(GPMPC_ERR_STATE, "refactor needs the second factor buffer (gpmpc_gp_reserve first)");
+    GPDev& g = h->P.gp[gp_id];
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const int cpad = (h->gp_cap[gp_id] + 15) / 16 * 16, ct = cpad / 16;
+    // the model changes with the first launch queued: the cache must not serve its old rows
+    bump_lin(h);
+    GPRefactor a{};
+    a.rows = h->gp_rows[gp_id];
+    a.tX = h->gp_tiles[gp_id];
+    a.tW = h->gp_tiles[gp_id] + (size_t)ct * 64;
+    a.linvT = h->gp_linvT[gp_id];
+    a.A = h->gp_linvT_alt[gp_id];
+    a.y = y_dev;
+    a.npad = h->gp_npad[gp_id];
+    a.n = g.n;
+    a.d = h->md.gp_dim[gp_id];
+    for (int k = 0; k < 3; ++k) a.xbar[k] = g.xbar[k];
+    a.inv_ell2 = 1.0 / (lengthscale * lengthscale);
+    a.sf2 = outputscale;
+    a.sn2 = noise;
+    a.dinv = h->gp_rfc[gp_id];
+    a.w = a.dinv + (size_t)ct * 256;
+    a.ym = a.w + cpad;
+    a.mask = reinterpret_cast<int32_t*>(a.ym + cpad);
+    a.flag = reinterpret_cast<int32_t*>(a.ym + cpad + cpad / 2);
+    a.ok = ok_dev;
+    HIPCHK(launch_gp_refactor(a, s));
+    // every kernel reads the hyperparameters from the handle: they change with the factor
+    g.inv_ell2 = a.inv_ell2;
+    g.sf2 = a.sf2;
+    g.sn2 = a.sn2;
     return GPMPC_OK;
 }
 

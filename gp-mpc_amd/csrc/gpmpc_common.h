@@ -327,9 +327,35 @@ struct GPDrop {
     int32_t* ok;          // the caller's status word of this block, may be null
 };
 
-// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip).
+// A from-scratch factorisation of an exact GP from its device-resident rows (gp_refactor.hip;
+// gpmpc_gp_refactor fills it).  Khat and its factor are built in A, the GP's spare factor buffer; the
+// live one receives (L^-1)^T in full, zeros included, at the stride it has.
+struct GPRefactor {
+    double* rows;         // [>= npad][4], GPDev::rows: inputs read, rows[.][3] rewritten
+    double* tX;           // GPDev::tX / tW (capacity-sized regions), rewritten for the new lengthscale
+    double* tW;
+    double* linvT;        // [npad][npad], the live factor: its diagonal is read for the inert mask first
+    double* A;            // [npad][npad] work space (the second factor buffer)
+    const double* y;      // [n] targets in row order (device); inert rows' entries are not read into sums
+    int32_t npad;         // n rounded up to 16 (unchanged)
+    int32_t n;
+    int32_t d;
+    double xbar[3];       // the tile pack's centre (unchanged)
+    double inv_ell2, sf2, sn2;   // the hyperparameters the GP is left with
+    // scratch of the GP: L_kk^-1 [npad/16][16][16], w = L^-1 y [npad], the targets with the inert rows'
+    // zeroed [npad], the inert mask [npad], the status
+    double* dinv;
+    double* w;
+    double* ym;
+    int32_t* mask;
+    int32_t* flag;
+    int32_t* ok;          // the caller's status word, may be null
+};
+
+// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip, gp_refactor.hip).
 hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream);
 hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream);
+hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream);
 // count < 0: the whole batch; else ranks first .. first + count - 1 of order[] (launch_sqp_order)
 hipError_t launch_sqp(const ProblemDev& P, const StateDev& S, const StepIO& io, int batch, hipStream_t stream,
                       int first = 0, int count = -1);

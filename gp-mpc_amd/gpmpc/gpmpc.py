@@ -243,6 +243,49 @@ class GPMPC:
             self.gaussian_process[i].append_data(X, y)
         return flags
 
+    def refresh_gps(self, hyperparameters: list | None = None) -> list[torch.Tensor]:
+        """Factorise every GP on the solver handle again from scratch, on the device
+        (``BatchSolver.refactor_gp``, queued on the current stream, no upload): from the handle's own
+        inputs and the Python GP's ``train_targets``.  ``hyperparameters[g] = (lengthscale,
+        outputscale, noise)`` applies new hyperparameters to GP g, on the handle and on the Python
+        object (``GaussianProcess.set_hyperparameters``); by default every GP keeps its own, and the
+        call only sheds the rounding that appends and drops have accumulated.  Returns the status
+        flags per GP (device tensors; a 0 means that GP must be uploaded again).  Same preconditions
+        as ``append_data``; not available in sparse (FITC) mode."""
+        if self.sparse:
+            raise _lib.GPMPCError("refresh_gps: not available in sparse (FITC) mode")
+        assert self.gaussian_process is not None and not self._requires_recompile, \
+            "GP model must be uploaded (call reset())"
+        if hyperparameters is not None and len(hyperparameters) != len(self.gp_idx):
+            raise ValueError(f"expected {len(self.gp_idx)} (lengthscale, outputscale, noise) triples")
+        flags = []
+        for i, gp in enumerate(self.gaussian_process):
+            hyp = (gp.lengthscale, gp.outputscale, gp.noise) if hyperparameters is None else \
+                tuple(float(v) for v in hyperparameters[i])
+            flags.append(self.solver.refactor_gp(i, gp.train_targets, *hyp))
+            if hyperparameters is not None:
+                gp.set_hyperparameters(*hyp)
+        return flags
+
+    def refit_hyperparameters(self, lr: float, iterations: int) -> list[torch.Tensor]:
+        """Refit the hyperparameters of the uploaded GPs on their current data (``fit_gp``, or
+        ``fit_gp_allreduce`` under more than one rank, as ``train_gp`` chooses) and apply them on the
+        device (``refresh_gps``): no upload, and the controller needs no ``reset()``.  Returns
+        ``refresh_gps``' flags."""
+        if self.sparse:
+            raise _lib.GPMPCError("refit_hyperparameters: not available in sparse (FITC) mode")
+        assert self.gaussian_process is not None and not self._requires_recompile, \
+            "GP model must be uploaded (call reset())"
+        from . import distributed as D
+
+        _, size = D.world()
+        for gp in self.gaussian_process:
+            if size > 1:
+                D.fit_gp_allreduce(gp, n_train=iterations, lr=lr)
+            else:
+                fit_gp(gp, n_train=iterations, lr=lr, device=self.device)
+        return self.refresh_gps()
+
     def precompute_sparse_posterior_mean(self, n_samples: int):
         """FITC weights on random training rows (`gpmpc/gpmpc.py:377-400`), computed where the
         GP lives (the MI355X for a GP fitted by ``train_gp``)."""

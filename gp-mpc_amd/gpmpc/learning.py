@@ -59,7 +59,7 @@ def run_evaluation(ctrl, x0: np.ndarray, steps: int, tstep0: np.ndarray | None =
 
 
 def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, seed: int,
-                       tstep0: np.ndarray | None = None, sliding: bool = False) -> dict:
+                       tstep0: np.ndarray | None = None, sliding: bool = False, refresh_every: int = 0) -> dict:
     """A closed-loop episode that learns while it runs: after every plant step a seeded random
     choice of ``append_per_step`` of the step's B transitions is preprocessed
     (``GPMPC.preprocess_data``) and appended to the uploaded GPs (``GPMPC.append_data``, a
@@ -80,7 +80,7 @@ def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, s
     obs = torch.tensor(np.asarray(x0, dtype=np.float64).reshape(B, -1), device=dev)
     ts = torch.tensor(np.zeros(B) if tstep0 is None else tstep0, dtype=torch.int32, device=dev)
     data = {"obs": [obs.cpu().numpy()], "action": [], "status": [], "inference_time_data": [], "n_train": []}
-    for _ in range(steps):
+    for step in range(steps):
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         u = ctrl.select_action_batch(obs, ts.clone())
@@ -98,6 +98,8 @@ def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, s
             inputs, targets = ctrl.preprocess_data(data["obs"][-2][pick], data["action"][-1][pick],
                                                    data["obs"][-1][pick])
             ctrl.append_data(inputs, targets, evict_oldest=sliding)
+        if refresh_every > 0 and (step + 1) % refresh_every == 0:
+            ctrl.refresh_gps()
         data["n_train"].append(solver.gp_size(0)[0])
     return {k: np.array(v) for k, v in data.items()}
 

@@ -206,6 +206,27 @@ class BatchSolver:
         _lib.check(self.lib.gpmpc_gp_drop_oldest(self._h, int(gp_id), m, flags.data_ptr(), self._stream()))
         return flags
 
+    def refactor_gp(self, gp_id: int, y, lengthscale: float, outputscale: float, noise: float) -> torch.Tensor:
+        """Factorise the handle's GP ``gp_id`` again from scratch on the current stream
+        (gpmpc_gp_refactor): from the handle's own training inputs, the targets ``y`` (n,) of its n
+        current rows in row order (``gp_size``; inert rows included, their entries are ignored) and
+        the hyperparameters given.  With the GP's current hyperparameters it refreshes a factor that
+        appends and drops have let drift; with new ones it applies a refit.  cuda or host tensors (or
+        arrays); no synchronisation of its own.  Needs ``reserve_gp``.  Returns the status flag, a
+        device int32 tensor [1] (1: every live target finite and every pivot finite and positive; 0:
+        the GP's contents are unspecified, upload it again).  The Python GP objects are not touched
+        (``GaussianProcess.set_hyperparameters``)."""
+        y = torch.as_tensor(y).to(self.device, torch.float64).reshape(-1).contiguous()
+        # (an unset GP is the library's refusal, like every other precondition)
+        n = self.gp_size(gp_id)[0] if y.numel() else 0
+        if y.numel() and y.shape[0] != n:
+            raise ValueError(f"GP {gp_id} has {n} training rows, got {y.shape[0]} targets")
+        flag = torch.empty(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gpmpc_gp_refactor(self._h, int(gp_id), y.data_ptr() if y.numel() else None,
+                                              float(lengthscale), float(outputscale), float(noise), flag.data_ptr(),
+                                              self._stream()))
+        return flag
+
     def gp_size(self, gp_id: int) -> tuple[int, int]:
         """(training rows, capacity) of the handle's GP ``gp_id`` (gpmpc_gp_size)."""
         n, cap = ctypes.c_int32(), ctypes.c_int32()

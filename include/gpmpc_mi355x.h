@@ -142,6 +142,30 @@ gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const do
  * writes the factor into the second buffer a reserve allocates (GPMPC_ERR_STATE). */
 gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int32_t* ok_dev, void* stream);
 
+/* Factorise GP gp_id again from scratch on `stream`, from what the device already holds: the
+ * handle's own training inputs, the caller's device targets y_dev [n] (float64, the targets of the
+ * GP's n current rows in row order; n as gpmpc_gp_size reports it, inert rows included) and the
+ * hyperparameters passed in.  With the current hyperparameters it refreshes a factor that appends
+ * and drops have let drift; with new ones it applies a hyperparameter refit.  No host
+ * synchronisation, nothing read back, nothing allocated (csrc/gp_refactor.hip: a blocked Cholesky
+ * factorisation and triangular inverse in 16-wide panels, 2 ceil(n/16) + 4 launches).  Afterwards
+ * the GP is what gpmpc_set_gp would have produced for (X, y, lengthscale, outputscale, noise):
+ * (L^-1)^T of k(X,X) + noise I at the stride it had, alpha = K^-1 y, and the MFMA tile pack
+ * rewritten in full (its input part depends on the lengthscale); xbar, n and the capacity are
+ * unchanged.  Inert rows (rejected append blocks, recognised by the zero on the old factor's
+ * diagonal) take part as identity rows and stay inert; their y_dev entries are never read into a
+ * sum and may be anything, NaN included.
+ * ok_dev: device int32 [1], may be NULL; 1 when every target of a live row is finite and every
+ * pivot was finite and positive, else 0.  After a 0 the contents of the GP are unspecified (nothing
+ * is accessed out of bounds): upload it again with gpmpc_set_gp before it is used.
+ * Refused, with the GP unchanged: y_dev NULL or a hyperparameter that is not finite and positive
+ * (GPMPC_ERR_ARG); GP not set, set without Linv, a FITC upload (Xv != X), a LOVE root installed
+ * (drop it first with gpmpc_set_gp_variance_root(R = NULL)), or no gpmpc_gp_reserve since
+ * gpmpc_set_gp -- the work space is the second factor buffer and scratch a reserve allocates
+ * (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_gp_refactor(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double lengthscale,
+                               double outputscale, double noise, int32_t* ok_dev, void* stream);
+
 /* Training rows of GP gp_id (inert rows included) and its capacity; either may be NULL. */
 gpmpc_status gpmpc_gp_size(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* capacity);
 
