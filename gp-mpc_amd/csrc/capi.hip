@@ -9,6 +9,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "gp_tile.h"   // (the tile pack's slot mapping)
 #include "gpmpc_common.h"
 
 using namespace gpmpc;
@@ -56,6 +57,57 @@ bool model_dims(int id, ModelDims& m) {
     }
     return false;
 }
+
+// What the handle keeps of one GP next to ProblemDev::gp[g] (GPDev: what the kernels read)
+struct GPSlot {
+    bool set = false, exact = false;   // uploaded; exactly (Xv == X)
+    int npad = 0, cap = 0;   // padded rows of the factor; training rows the buffers hold (the uploaded size until reserved)
+    double *rows = nullptr, *vrows = nullptr, *linvT = nullptr, *tiles = nullptr;   // tiles: tX | tW (MFMA tile pack)
+    double* linvT_alt = nullptr;   // second factor buffer: the factor moves to it when npad changes, the two swap roles
+    double *app = nullptr, *drp = nullptr, *rfc = nullptr;   // scratch of gpmpc_gp_append / _drop_oldest / _refactor
+    double* vroot = nullptr;       // LOVE root (tightening only), its padded columns and its rank
+    int vroot_cols = 0, vroot_rank = 0;
+    // The slot's device buffers: the kReserved ones gpmpc_gp_reserve replaces, then the others
+    static constexpr int kReserved = 7, kBuffers = 9;
+    static constexpr double* GPSlot::*kBuffer[kBuffers] = {&GPSlot::rows,  &GPSlot::tiles, &GPSlot::linvT,
+                                                            &GPSlot::linvT_alt, &GPSlot::app, &GPSlot::drp,
+                                                            &GPSlot::rfc, &GPSlot::vrows, &GPSlot::vroot};
+    hipError_t release(int count) {   // frees and clears the first `count` of them; returns the first error
+        hipError_t first = hipSuccess;
+        for (int i = 0; i < count; ++i) {
+            double*& p = this->*kBuffer[i];
+            const hipError_t e = p ? hipFree(p) : hipSuccess;
+            if (first == hipSuccess) first = e;
+            p = nullptr;
+        }
+        return first;
+    }
+    void drop_root() {   // back to the exact variance: root, columns and rank together
+        if (vroot) (void)hipFree(vroot);
+        vroot = nullptr;
+        vroot_cols = vroot_rank = 0;
+    }
+};
+// Scratch of the three device-side updates for a capacity of c (padded) rows, in doubles: the offsets
+// gpmpc_gp_append / _drop_oldest / _refactor carve their buffer at and the size (end) gpmpc_gp_reserve allocates
+struct AppendLayout {   // W^T [16][c] | per-tile means [c/16][16] | L_b^-1 [256] | beta [16] | status word
+    size_t c, wt = 0, pmean = 16 * c, lbinv = pmean + c, beta = lbinv + 256, flag = beta + 16, end = flag + 1;
+};
+// V^T [16][c] | M21 g [c] | E_T, D_T [c/16][256] each | staged rows [c][4], tX, tW [c/16][64] each | status word
+struct DropLayout {
+    size_t c, vt = 0, w = 16 * c, et = w + c, dt = et + 16 * c, srows = dt + 16 * c, stX = srows + 4 * c,
+              stW = stX + 4 * c, flag = stW + 4 * c, end = flag + 1;
+};
+// L_kk^-1 [c/16][256] | w [c] | masked targets [c] | the inert mask [c] int32 (in c/2 doubles) | status word
+struct RefactorLayout {
+    size_t c, dinv = 0, w = 16 * c, ym = w + c, mask = ym + c, flag = mask + c / 2, end = flag + 1;
+};
+constexpr bool layouts_hold(size_t c) {
+    return AppendLayout{c}.end == 16 * c + c + 256 + 16 + 1 && AppendLayout{c}.flag == 17 * c + 272 &&
+           DropLayout{c}.end == 61 * c + 1 && DropLayout{c}.srows == 49 * c && RefactorLayout{c}.mask == 18 * c &&
+           RefactorLayout{c}.end == 18 * c + c / 2 + 1;
+}
+static_assert(layouts_hold(16) && layouts_hold(4096), "scratch layouts of the GP updates changed size or offsets");
 }  // namespace
 
 struct gpmpc_handle {
@@ -66,7 +118,6 @@ struct gpmpc_handle {
     ModelDims md{};
     int nb = 0;
     bool model_set = false, ref_set = false;
-    bool gp_set[kMaxGP] = {false, false, false, false};
     bool any_prev = false;
     ProblemDev P{};
     // device state
@@ -83,23 +134,7 @@ struct gpmpc_handle {
     double* tgain = nullptr;        // [H][nb][n_unc] tightening gain table (ProblemDev::tgain)
     double plant_params_host[kMaxParams] = {0};
     bool plant_params_valid = false;
-    double* gp_rows[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
-    double* gp_vrows[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
-    double* gp_linvT[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
-    double* gp_tiles[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};   // tX | tW (MFMA tile pack)
-    int gp_npad[kMaxGP] = {0, 0, 0, 0};
-    // appending (gpmpc_gp_reserve / gpmpc_gp_append): training rows the GP's buffers hold (the uploaded
-    // size until reserved), whether the upload was exact (Xv == X), the second factor buffer the
-    // factor moves to when npad grows (the two swap roles), and the append kernels' scratch
-    int gp_cap[kMaxGP] = {0, 0, 0, 0};
-    bool gp_exact[kMaxGP] = {false, false, false, false};
-    double* gp_linvT_alt[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
-    double* gp_app[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};
-    double* gp_drp[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};   // gpmpc_gp_drop_oldest's scratch and staging
-    double* gp_rfc[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};   // gpmpc_gp_refactor's scratch
-    double* gp_vroot[kMaxGP] = {nullptr, nullptr, nullptr, nullptr};   // LOVE roots (tightening only)
-    int gp_vroot_cols[kMaxGP] = {0, 0, 0, 0};
-    int gp_vroot_rank[kMaxGP] = {0, 0, 0, 0};
+    GPSlot gp[kMaxGP];
     // optional per-kernel HIP-event timing (bench.py's roofline leg)
     bool profiling = false;
     std::vector<hipEvent_t> ev_pool;
@@ -246,17 +281,7 @@ static void free_handle(gpmpc_handle* h) {
     if (h->cost) (void)hipFree(h->cost);
     if (h->scratch_i) (void)hipFree(h->scratch_i);
     if (h->scratch_d) (void)hipFree(h->scratch_d);
-    for (int g = 0; g < kMaxGP; ++g) {
-        if (h->gp_rows[g]) (void)hipFree(h->gp_rows[g]);
-        if (h->gp_vrows[g]) (void)hipFree(h->gp_vrows[g]);
-        if (h->gp_linvT[g]) (void)hipFree(h->gp_linvT[g]);
-        if (h->gp_tiles[g]) (void)hipFree(h->gp_tiles[g]);
-        if (h->gp_vroot[g]) (void)hipFree(h->gp_vroot[g]);
-        if (h->gp_linvT_alt[g]) (void)hipFree(h->gp_linvT_alt[g]);
-        if (h->gp_app[g]) (void)hipFree(h->gp_app[g]);
-        if (h->gp_drp[g]) (void)hipFree(h->gp_drp[g]);
-        if (h->gp_rfc[g]) (void)hipFree(h->gp_rfc[g]);
-    }
+    for (GPSlot& gs : h->gp) (void)gs.release(GPSlot::kBuffers);
     delete h;
 }
 
@@ -462,47 +487,41 @@ gpmpc_status gpmpc_set_gp(gpmpc_handle* h, int32_t gp_id, int32_t n, int32_t d, 
     double* tW = tiles.data() + (size_t)ntile * 64;
     const double m2c = 1.0 / (lengthscale * lengthscale);
     for (int i = 0; i < n; ++i) {
-        // MFMA C/D rows: register q of lane group grp holds row grp + 4q
-        const int t = i / 16, r = i % 16, grp = r % 4, q = r / 4;
+        const TileSlot sl = tile_slot(i);   // (gp_tile.h: the layout the device-side updates write too)
         double xc[3] = {0.0, 0.0, 0.0}, sq = 0.0;
         for (int k = 0; k < d; ++k) {
             xc[k] = X[(size_t)i * d + k] - xbar[k];
             sq += xc[k] * xc[k];
-            tX[(size_t)t * 64 + r * 4 + k] = m2c * xc[k];
+            tX[tile_x_at(sl) + k] = m2c * xc[k];
         }
-        tX[(size_t)t * 64 + r * 4 + 3] = c * sq;
+        tX[tile_x_at(sl) + 3] = c * sq;
         const double wv[4] = {alpha[i], alpha[i] * xc[0], alpha[i] * xc[1], alpha[i] * xc[2]};
-        for (int j = 0; j < 4; ++j) tW[(size_t)t * 64 + (grp * 4 + j) * 4 + q] = wv[j];
+        for (int j = 0; j < 4; ++j) tW[tile_w_at(sl, j)] = wv[j];
     }
-    for (double** p : {&h->gp_rows[gp_id], &h->gp_vrows[gp_id], &h->gp_linvT[gp_id], &h->gp_tiles[gp_id],
-                       &h->gp_vroot[gp_id], &h->gp_linvT_alt[gp_id],
-                       &h->gp_app[gp_id], &h->gp_drp[gp_id], &h->gp_rfc[gp_id]}) {   // (a LOVE root belongs to the previous training set)
-        if (*p) HIPCHK(hipFree(*p));
-        *p = nullptr;
-    }
-    h->gp_vroot_cols[gp_id] = 0;
-    h->gp_vroot_rank[gp_id] = 0;
-    HIPCHK(hipMalloc(&h->gp_rows[gp_id], rows.size() * sizeof(double)));
-    HIPCHK(hipMemcpy(h->gp_rows[gp_id], rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&h->gp_tiles[gp_id], tiles.size() * sizeof(double)));
-    HIPCHK(hipMemcpy(h->gp_tiles[gp_id], tiles.data(), tiles.size() * sizeof(double), hipMemcpyHostToDevice));
+    GPSlot& gs = h->gp[gp_id];
+    HIPCHK(gs.release(GPSlot::kBuffers));   // (a LOVE root belongs to the previous training set)
+    gs.vroot_cols = gs.vroot_rank = 0;
+    HIPCHK(hipMalloc(&gs.rows, rows.size() * sizeof(double)));
+    HIPCHK(hipMemcpy(gs.rows, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&gs.tiles, tiles.size() * sizeof(double)));
+    HIPCHK(hipMemcpy(gs.tiles, tiles.data(), tiles.size() * sizeof(double), hipMemcpyHostToDevice));
     if (!exact) {
-        HIPCHK(hipMalloc(&h->gp_vrows[gp_id], vrows.size() * sizeof(double)));
-        HIPCHK(hipMemcpy(h->gp_vrows[gp_id], vrows.data(), vrows.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&gs.vrows, vrows.size() * sizeof(double)));
+        HIPCHK(hipMemcpy(gs.vrows, vrows.data(), vrows.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     if (Linv) {
         std::vector<double> lt((size_t)npad * npad, 0.0);
         for (int i = 0; i < nv; ++i)
             for (int j = 0; j <= i; ++j) lt[(size_t)j * npad + i] = Linv[(size_t)i * nv + j];  // (L^-1)^T
-        HIPCHK(hipMalloc(&h->gp_linvT[gp_id], lt.size() * sizeof(double)));
-        HIPCHK(hipMemcpy(h->gp_linvT[gp_id], lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&gs.linvT, lt.size() * sizeof(double)));
+        HIPCHK(hipMemcpy(gs.linvT, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     GPDev& g = h->P.gp[gp_id];
-    g.rows = h->gp_rows[gp_id];
-    g.vrows = exact ? h->gp_rows[gp_id] : h->gp_vrows[gp_id];
-    g.linvT = h->gp_linvT[gp_id];
-    g.tX = h->gp_tiles[gp_id];
-    g.tW = h->gp_tiles[gp_id] + (size_t)ntile * 64;
+    g.rows = gs.rows;
+    g.vrows = exact ? gs.rows : gs.vrows;
+    g.linvT = gs.linvT;
+    g.tX = gs.tiles;
+    g.tW = gs.tiles + (size_t)ntile * 64;
     g.ntile = ntile;
     for (int k = 0; k < 3; ++k) g.xbar[k] = xbar[k];
     g.n = n;
@@ -511,88 +530,91 @@ gpmpc_status gpmpc_set_gp(gpmpc_handle* h, int32_t gp_id, int32_t n, int32_t d, 
     g.inv_ell2 = 1.0 / (lengthscale * lengthscale);
     g.sf2 = outputscale;
     g.sn2 = noise;
-    h->gp_npad[gp_id] = npad;
-    h->gp_cap[gp_id] = n;   // (appending needs gpmpc_gp_reserve)
-    h->gp_exact[gp_id] = exact;
-    h->gp_set[gp_id] = true;
+    gs.npad = npad;
+    gs.cap = n;   // (appending needs gpmpc_gp_reserve)
+    gs.exact = exact;
+    gs.set = true;
     bump_lin(h);
     return GPMPC_OK;
 }
 
-// Scratch of the append kernels for a capacity of cpad rows (GPAppend): W^T [16][cpad] | per-tile
-// means [cpad/16][16] | L_b^-1 [256] | beta [16] | status word
-static size_t app_scratch_doubles(int cpad) { return (size_t)16 * cpad + cpad + 256 + 16 + 1; }
-// Scratch and staging of the drop kernels for a capacity of cpad rows (GPDrop): V^T [16][cpad] | M21 g
-// [cpad] | E_T [cpad/16][256] | D_T [cpad/16][256] | staged rows [cpad][4] | tX [cpad/16][64] | tW
-// [cpad/16][64] | status word
-static size_t drop_scratch_doubles(int cpad) { return (size_t)(16 + 1 + 16 + 16 + 4 + 4 + 4) * cpad + 1; }
-// Scratch of the refactorisation for a capacity of cpad rows (GPRefactor): L_kk^-1 [cpad/16][256] | w [cpad] |
-// masked targets [cpad] | the inert mask [cpad] int32 (in cpad/2 doubles) | status word
-static size_t refactor_scratch_doubles(int cpad) { return (size_t)(16 + 2) * cpad + cpad / 2 + 1; }
+// A device-side update as the refusals word it ("append" needs ..; only an exact GP "takes appended rows"; a LOVE root
+// belongs to "the old training set") and its scratch, which comes with the second factor buffer (null: not asked for)
+struct GPUpdate {
+    const char *verb, *takes, *root_of;
+    double* GPSlot::*scratch;
+};
+static const GPUpdate kAppend{"append", "takes appended rows", "the old training set", nullptr};
+static const GPUpdate kDrop{"drop", "drops rows", "the old training set", &GPSlot::drp};
+static const GPUpdate kRefactor{"refactor", "is refactorised", "the old factor", &GPSlot::rfc};
 
-gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) {
+// What the three updates ask first, in this order (bad_args: what is wrong with the call's own arguments, or
+// null).  gpmpc_gp_reserve asks the same up to the exact upload (factor = false).
+static gpmpc_status gp_update_ready(gpmpc_handle* h, int gp_id, const GPUpdate& op, const char* bad_args,
+                                    bool factor = true) {
     if (!h) return fail(GPMPC_ERR_ARG, "null handle");
     if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
-    if (!h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
-    if (!h->gp_exact[gp_id]) return fail(GPMPC_ERR_STATE, "FITC upload (Xv != X): only an exact GP takes appended rows");
+    if (bad_args) return fail(GPMPC_ERR_ARG, bad_args);
+    const GPSlot& gs = h->gp[gp_id];
+    if (!gs.set) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
+    if (!gs.exact) return fail(GPMPC_ERR_STATE, std::string("FITC upload (Xv != X): only an exact GP ") + op.takes);
+    if (!factor) return GPMPC_OK;
+    if (!gs.linvT) return fail(GPMPC_ERR_STATE, std::string(op.verb) + " needs Linv (the GP was set without it)");
+    if (gs.vroot)
+        return fail(GPMPC_ERR_STATE, std::string("a LOVE root is installed: it belongs to ") + op.root_of +
+                                         " (drop it first, gpmpc_set_gp_variance_root with R = NULL)");
+    if (op.scratch && (!(gs.*op.scratch) || !gs.linvT_alt))
+        return fail(GPMPC_ERR_STATE, std::string(op.verb) + " needs the second factor buffer (gpmpc_gp_reserve first)");
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) {
+    const gpmpc_status ready = gp_update_ready(h, gp_id, kAppend, nullptr, false);
+    if (ready != GPMPC_OK) return ready;
+    GPSlot& gs = h->gp[gp_id];
     GPDev& g = h->P.gp[gp_id];
     if (capacity < g.n) return fail(GPMPC_ERR_ARG, "capacity below the GP's " + std::to_string(g.n) + " training rows");
     if (capacity > (1 << 15)) return fail(GPMPC_ERR_ARG, "capacity above 32768 rows");
     (void)hipSetDevice(h->device);
     HIPCHK(hipDeviceSynchronize());   // a setup call: nothing queued still reads the buffers replaced below
     const size_t cpad = ((size_t)capacity + 15) / 16 * 16, ct = cpad / 16;
-    const size_t npad = h->gp_npad[gp_id], nt = g.ntile;
-    const bool lin = h->gp_linvT[gp_id] != nullptr;
-    // everything is allocated and filled before the handle changes
-    double *rows = nullptr, *tiles = nullptr, *la = nullptr, *lb = nullptr, *app = nullptr, *drp = nullptr, *rfc = nullptr;
-    auto drop = [&]() {
-        for (double* p : {rows, tiles, la, lb, app, drp, rfc})
-            if (p) (void)hipFree(p);
+    const size_t npad = gs.npad, nt = g.ntile;
+    const bool lin = gs.linvT != nullptr;
+    // everything is allocated and filled before the handle changes: `fresh` holds the new buffers
+    GPSlot fresh;
+    const struct { double** p; size_t doubles; bool zero; } want[] = {
+        {&fresh.rows, cpad * 4, true},
+        {&fresh.tiles, 2 * ct * 64, true},
+        {&fresh.linvT, lin ? cpad * cpad : 0, false},
+        {&fresh.linvT_alt, lin ? cpad * cpad : 0, false},
+        {&fresh.app, lin ? AppendLayout{cpad}.end : 0, true},
+        {&fresh.drp, lin ? DropLayout{cpad}.end : 0, true},
+        {&fresh.rfc, lin ? RefactorLayout{cpad}.end : 0, true},
     };
-    hipError_t e = hipMalloc(&rows, cpad * 4 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&tiles, 2 * ct * 64 * sizeof(double));
-    if (e == hipSuccess && lin) e = hipMalloc(&la, cpad * cpad * sizeof(double));
-    if (e == hipSuccess && lin) e = hipMalloc(&lb, cpad * cpad * sizeof(double));
-    if (e == hipSuccess && lin) e = hipMalloc(&app, app_scratch_doubles((int)cpad) * sizeof(double));
-    if (e == hipSuccess && lin) e = hipMalloc(&drp, drop_scratch_doubles((int)cpad) * sizeof(double));
-    if (e == hipSuccess && lin) e = hipMalloc(&rfc, refactor_scratch_doubles((int)cpad) * sizeof(double));
-    if (e != hipSuccess) {
-        drop();
-        return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    e = hipMemset(rows, 0, cpad * 4 * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(tiles, 0, 2 * ct * 64 * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(rows, h->gp_rows[gp_id], npad * 4 * sizeof(double), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy(tiles, g.tX, nt * 64 * sizeof(double), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy(tiles + ct * 64, g.tW, nt * 64 * sizeof(double), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess && lin) e = hipMemset(app, 0, app_scratch_doubles((int)cpad) * sizeof(double));
-    if (e == hipSuccess && lin) e = hipMemset(drp, 0, drop_scratch_doubles((int)cpad) * sizeof(double));
-    if (e == hipSuccess && lin) e = hipMemset(rfc, 0, refactor_scratch_doubles((int)cpad) * sizeof(double));
+    hipError_t e = hipSuccess;
+    auto undo = [&](gpmpc_status st, const char* what) {
+        (void)fresh.release(GPSlot::kReserved);
+        return fail(st, std::string(what) + hipGetErrorString(e));
+    };
+    for (const auto& w : want)
+        if (e == hipSuccess && w.doubles) e = hipMalloc(w.p, w.doubles * sizeof(double));
+    if (e != hipSuccess) return undo(GPMPC_ERR_NOMEM, "hipMalloc: ");
+    for (const auto& w : want)
+        if (e == hipSuccess && w.doubles && w.zero) e = hipMemset(*w.p, 0, w.doubles * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(fresh.rows, gs.rows, npad * 4 * sizeof(double), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy(fresh.tiles, g.tX, nt * 64 * sizeof(double), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy(fresh.tiles + ct * 64, g.tW, nt * 64 * sizeof(double), hipMemcpyDeviceToDevice);
     // the factor keeps its stride npad (the variance kernels' layout) at the head of the first buffer
-    if (e == hipSuccess && lin)
-        e = hipMemcpy(la, h->gp_linvT[gp_id], npad * npad * sizeof(double), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && lin) e = hipMemcpy(fresh.linvT, gs.linvT, npad * npad * sizeof(double), hipMemcpyDeviceToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        drop();
-        return fail(GPMPC_ERR_HIP, std::string("gpmpc_gp_reserve: ") + hipGetErrorString(e));
-    }
-    for (double** p : {&h->gp_rows[gp_id], &h->gp_tiles[gp_id], &h->gp_linvT[gp_id], &h->gp_linvT_alt[gp_id],
-                       &h->gp_app[gp_id], &h->gp_drp[gp_id], &h->gp_rfc[gp_id]}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    h->gp_rows[gp_id] = rows;
-    h->gp_tiles[gp_id] = tiles;
-    h->gp_linvT[gp_id] = la;
-    h->gp_linvT_alt[gp_id] = lb;
-    h->gp_app[gp_id] = app;
-    h->gp_drp[gp_id] = drp;
-    h->gp_rfc[gp_id] = rfc;
-    g.rows = g.vrows = rows;
-    g.linvT = la;
-    g.tX = tiles;
-    g.tW = tiles + ct * 64;
-    h->gp_cap[gp_id] = capacity;
+    if (e != hipSuccess) return undo(GPMPC_ERR_HIP, "gpmpc_gp_reserve: ");
+    (void)gs.release(GPSlot::kReserved);
+    for (int i = 0; i < GPSlot::kReserved; ++i) gs.*GPSlot::kBuffer[i] = fresh.*GPSlot::kBuffer[i];
+    g.rows = g.vrows = gs.rows;
+    g.linvT = gs.linvT;
+    g.tX = gs.tiles;
+    g.tW = gs.tiles + ct * 64;
+    gs.cap = capacity;
     bump_lin(h);
     return GPMPC_OK;
 }
@@ -600,54 +622,49 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
 gpmpc_status gpmpc_gp_size(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* capacity) {
     if (!h) return fail(GPMPC_ERR_ARG, "null handle");
     if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
-    if (!h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
+    if (!h->gp[gp_id].set) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
     if (n) *n = h->P.gp[gp_id].n;
-    if (capacity) *capacity = h->gp_cap[gp_id];
+    if (capacity) *capacity = h->gp[gp_id].cap;
     return GPMPC_OK;
 }
 
 gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const double* Xnew_dev, const double* ynew_dev,
                              int32_t* accepted_dev, void* stream) {
-    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
-    if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
-    if (m < 1 || !Xnew_dev || !ynew_dev) return fail(GPMPC_ERR_ARG, "no rows to append");
-    if (!h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
-    if (!h->gp_exact[gp_id]) return fail(GPMPC_ERR_STATE, "FITC upload (Xv != X): only an exact GP takes appended rows");
-    if (!h->gp_linvT[gp_id]) return fail(GPMPC_ERR_STATE, "append needs Linv (the GP was set without it)");
-    if (h->gp_vroot[gp_id])
-        return fail(GPMPC_ERR_STATE, "a LOVE root is installed: it belongs to the old training set (drop it first, "
-                                     "gpmpc_set_gp_variance_root with R = NULL)");
+    const gpmpc_status ready =
+        gp_update_ready(h, gp_id, kAppend, (m < 1 || !Xnew_dev || !ynew_dev) ? "no rows to append" : nullptr);
+    if (ready != GPMPC_OK) return ready;
+    GPSlot& gs = h->gp[gp_id];
     GPDev& g = h->P.gp[gp_id];
-    if ((int64_t)g.n + m > h->gp_cap[gp_id])
+    if ((int64_t)g.n + m > gs.cap)
         return fail(GPMPC_ERR_ARG, "capacity exceeded: " + std::to_string(g.n) + " + " + std::to_string(m) +
-                                       " rows, capacity " + std::to_string(h->gp_cap[gp_id]) + " (gpmpc_gp_reserve)");
+                                       " rows, capacity " + std::to_string(gs.cap) + " (gpmpc_gp_reserve)");
     (void)hipSetDevice(h->device);
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(order_after_last(h, s));
     StreamMark mark{h, s};
-    const int cpad = (h->gp_cap[gp_id] + 15) / 16 * 16, d = h->md.gp_dim[gp_id];
-    double* app = h->gp_app[gp_id];
+    const int cpad = (gs.cap + 15) / 16 * 16, d = h->md.gp_dim[gp_id];
+    const AppendLayout lay{(size_t)cpad};
     for (int done = 0, blk = 0; done < m; done += 16, ++blk) {
         const int mb = std::min(16, m - done);
-        const int n0 = g.n, npad0 = h->gp_npad[gp_id], npad1 = (n0 + mb + 15) / 16 * 16;
+        const int n0 = g.n, npad0 = gs.npad, npad1 = (n0 + mb + 15) / 16 * 16;
         // the model changes with the first launch queued: the cache must not serve its old rows
         bump_lin(h);
         if (npad1 > npad0) {
             // the factor moves to the other buffer at the new stride, the new border zeroed
-            double* dst = h->gp_linvT_alt[gp_id];
+            double* dst = gs.linvT_alt;
             const size_t p0 = (size_t)npad0 * sizeof(double), p1 = (size_t)npad1 * sizeof(double);
-            HIPCHK(hipMemcpy2DAsync(dst, p1, h->gp_linvT[gp_id], p0, p0, npad0, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpy2DAsync(dst, p1, gs.linvT, p0, p0, npad0, hipMemcpyDeviceToDevice, s));
             HIPCHK(hipMemset2DAsync(dst + npad0, p1, 0, p1 - p0, npad0, s));
             HIPCHK(hipMemsetAsync(dst + (size_t)npad0 * npad1, 0, (size_t)(npad1 - npad0) * p1, s));
-            std::swap(h->gp_linvT[gp_id], h->gp_linvT_alt[gp_id]);
-            g.linvT = h->gp_linvT[gp_id];
-            h->gp_npad[gp_id] = npad1;
+            std::swap(gs.linvT, gs.linvT_alt);
+            g.linvT = gs.linvT;
+            gs.npad = npad1;
         }
         GPAppend a{};
-        a.rows = h->gp_rows[gp_id];
-        a.tX = h->gp_tiles[gp_id];
-        a.tW = h->gp_tiles[gp_id] + (size_t)(cpad / 16) * 64;
-        a.linvT = h->gp_linvT[gp_id];
+        a.rows = gs.rows;
+        a.tX = gs.tiles;
+        a.tW = gs.tiles + (size_t)(cpad / 16) * 64;
+        a.linvT = gs.linvT;
         a.npad = npad1;
         a.n0 = n0;
         a.m = mb;
@@ -658,12 +675,12 @@ gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const do
         a.sn2 = g.sn2;
         a.Xnew = Xnew_dev + (size_t)done * d;
         a.ynew = ynew_dev + done;
-        a.wt = app;
+        a.wt = gs.app + lay.wt;
         a.ldw = cpad;
-        a.pmean = app + (size_t)16 * cpad;
-        a.lbinv = a.pmean + cpad;
-        a.beta = a.lbinv + 256;
-        a.flag = reinterpret_cast<int32_t*>(a.beta + 16);
+        a.pmean = gs.app + lay.pmean;
+        a.lbinv = gs.app + lay.lbinv;
+        a.beta = gs.app + lay.beta;
+        a.flag = reinterpret_cast<int32_t*>(gs.app + lay.flag);
         a.accepted = accepted_dev ? accepted_dev + blk : nullptr;
         HIPCHK(launch_gp_append(a, s));
         // the row count advances whether the block is accepted or written as inert rows
@@ -674,16 +691,9 @@ gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const do
 }
 
 gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int32_t* ok_dev, void* stream) {
-    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
-    if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
-    if (!h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
-    if (!h->gp_exact[gp_id]) return fail(GPMPC_ERR_STATE, "FITC upload (Xv != X): only an exact GP drops rows");
-    if (!h->gp_linvT[gp_id]) return fail(GPMPC_ERR_STATE, "drop needs Linv (the GP was set without it)");
-    if (h->gp_vroot[gp_id])
-        return fail(GPMPC_ERR_STATE, "a LOVE root is installed: it belongs to the old training set (drop it first, "
-                                     "gpmpc_set_gp_variance_root with R = NULL)");
-    if (!h->gp_drp[gp_id] || !h->gp_linvT_alt[gp_id])
-        return fail(GPMPC_ERR_STATE, "drop needs the second factor buffer (gpmpc_gp_reserve first)");
+    const gpmpc_status ready = gp_update_ready(h, gp_id, kDrop, nullptr);
+    if (ready != GPMPC_OK) return ready;
+    GPSlot& gs = h->gp[gp_id];
     GPDev& g = h->P.gp[gp_id];
     if (m < 1) return fail(GPMPC_ERR_ARG, "no rows to drop");
     if (m >= g.n)
@@ -693,19 +703,19 @@ gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(order_after_last(h, s));
     StreamMark mark{h, s};
-    const int cpad = (h->gp_cap[gp_id] + 15) / 16 * 16, ct = cpad / 16, d = h->md.gp_dim[gp_id];
-    double* rows = h->gp_rows[gp_id];
-    double* tX = h->gp_tiles[gp_id];
-    double* tW = h->gp_tiles[gp_id] + (size_t)ct * 64;
-    double* drp = h->gp_drp[gp_id];
+    const int cpad = (gs.cap + 15) / 16 * 16, ct = cpad / 16, d = h->md.gp_dim[gp_id];
+    const DropLayout lay{(size_t)cpad};
+    double* rows = gs.rows;
+    double* tX = gs.tiles;
+    double* tW = gs.tiles + (size_t)ct * 64;
     for (int done = 0, blk = 0; done < m; done += 16, ++blk) {
         const int mb = std::min(16, m - done);
-        const int n0 = g.n, npad0 = h->gp_npad[gp_id], n1 = n0 - mb, npad1 = (n1 + 15) / 16 * 16;
+        const int n0 = g.n, npad0 = gs.npad, n1 = n0 - mb, npad1 = (n1 + 15) / 16 * 16;
         // the model changes with the first launch queued: the cache must not serve its old rows
         bump_lin(h);
         GPDrop a{};
-        a.src = h->gp_linvT[gp_id];
-        a.dst = h->gp_linvT_alt[gp_id];
+        a.src = gs.linvT;
+        a.dst = gs.linvT_alt;
         a.rows = rows;
         a.tX = tX;
         a.npad0 = npad0;
@@ -714,15 +724,15 @@ gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int
         a.m = mb;
         a.d = d;
         for (int k = 0; k < 3; ++k) a.xbar[k] = g.xbar[k];
-        a.vt = drp;
+        a.vt = gs.drp + lay.vt;
         a.ldv = cpad;
-        a.w = a.vt + (size_t)16 * cpad;
-        a.et = a.w + cpad;
-        a.dt = a.et + (size_t)ct * 256;
-        a.srows = a.dt + (size_t)ct * 256;
-        a.stX = a.srows + (size_t)cpad * 4;
-        a.stW = a.stX + (size_t)ct * 64;
-        a.flag = reinterpret_cast<int32_t*>(a.stW + (size_t)ct * 64);
+        a.w = gs.drp + lay.w;
+        a.et = gs.drp + lay.et;
+        a.dt = gs.drp + lay.dt;
+        a.srows = gs.drp + lay.srows;
+        a.stX = gs.drp + lay.stX;
+        a.stW = gs.drp + lay.stW;
+        a.flag = reinterpret_cast<int32_t*>(gs.drp + lay.flag);
         a.ok = ok_dev ? ok_dev + blk : nullptr;
         HIPCHK(launch_gp_drop(a, s));
         // the staged rows and tile pack replace the live ones (disjoint buffers); what lies between the
@@ -737,9 +747,9 @@ gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int
             HIPCHK(hipMemsetAsync(tW + (size_t)npad1 * 4, 0, rb0 - rb, s));
         }
         // the two factor buffers swap roles
-        std::swap(h->gp_linvT[gp_id], h->gp_linvT_alt[gp_id]);
-        g.linvT = h->gp_linvT[gp_id];
-        h->gp_npad[gp_id] = npad1;
+        std::swap(gs.linvT, gs.linvT_alt);
+        g.linvT = gs.linvT;
+        gs.npad = npad1;
         g.n = g.nv = n1;
         g.ntile = (n1 + 15) / 16;
     }
@@ -748,47 +758,41 @@ gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int
 
 gpmpc_status gpmpc_gp_refactor(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double lengthscale,
                                double outputscale, double noise, int32_t* ok_dev, void* stream) {
-    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
-    if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
-    if (!y_dev) return fail(GPMPC_ERR_ARG, "no targets");
-    if (!(std::isfinite(lengthscale) && lengthscale > 0.0) || !(std::isfinite(outputscale) && outputscale > 0.0) ||
-        !(std::isfinite(noise) && noise > 0.0))
-        return fail(GPMPC_ERR_ARG, "hyperparameters must be finite and positive");
-    if (!h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
-    if (!h->gp_exact[gp_id]) return fail(GPMPC_ERR_STATE, "FITC upload (Xv != X): only an exact GP is refactorised");
-    if (!h->gp_linvT[gp_id]) return fail(GPMPC_ERR_STATE, "refactor needs Linv (the GP was set without it)");
-    if (h->gp_vroot[gp_id])
-        return fail(GPMPC_ERR_STATE, "a LOVE root is installed: it belongs to the old factor (drop it first, "
-                                     "gpmpc_set_gp_variance_root with R = NULL)");
-    if (!h->gp_rfc[gp_id] || !h->gp_linvT_alt[gp_id])
-        return fail(GPMPC_ERR_STATE, "refactor needs the second factor buffer (gpmpc_gp_reserve first)");
+    const bool hyp_ok = std::isfinite(lengthscale) && lengthscale > 0.0 && std::isfinite(outputscale) &&
+                        outputscale > 0.0 && std::isfinite(noise) && noise > 0.0;
+    const gpmpc_status ready =
+        gp_update_ready(h, gp_id, kRefactor,
+                        !y_dev ? "no targets" : !hyp_ok ? "hyperparameters must be finite and positive" : nullptr);
+    if (ready != GPMPC_OK) return ready;
+    GPSlot& gs = h->gp[gp_id];
     GPDev& g = h->P.gp[gp_id];
     (void)hipSetDevice(h->device);
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(order_after_last(h, s));
     StreamMark mark{h, s};
-    const int cpad = (h->gp_cap[gp_id] + 15) / 16 * 16, ct = cpad / 16;
+    const int cpad = (gs.cap + 15) / 16 * 16;
+    const RefactorLayout lay{(size_t)cpad};
     // the model changes with the first launch queued: the cache must not serve its old rows
     bump_lin(h);
     GPRefactor a{};
-    a.rows = h->gp_rows[gp_id];
-    a.tX = h->gp_tiles[gp_id];
-    a.tW = h->gp_tiles[gp_id] + (size_t)ct * 64;
-    a.linvT = h->gp_linvT[gp_id];
-    a.A = h->gp_linvT_alt[gp_id];
+    a.rows = gs.rows;
+    a.tX = gs.tiles;
+    a.tW = gs.tiles + (size_t)(cpad / 16) * 64;
+    a.linvT = gs.linvT;
+    a.A = gs.linvT_alt;
     a.y = y_dev;
-    a.npad = h->gp_npad[gp_id];
+    a.npad = gs.npad;
     a.n = g.n;
     a.d = h->md.gp_dim[gp_id];
     for (int k = 0; k < 3; ++k) a.xbar[k] = g.xbar[k];
     a.inv_ell2 = 1.0 / (lengthscale * lengthscale);
     a.sf2 = outputscale;
     a.sn2 = noise;
-    a.dinv = h->gp_rfc[gp_id];
-    a.w = a.dinv + (size_t)ct * 256;
-    a.ym = a.w + cpad;
-    a.mask = reinterpret_cast<int32_t*>(a.ym + cpad);
-    a.flag = reinterpret_cast<int32_t*>(a.ym + cpad + cpad / 2);
+    a.dinv = gs.rfc + lay.dinv;
+    a.w = gs.rfc + lay.w;
+    a.ym = gs.rfc + lay.ym;
+    a.mask = reinterpret_cast<int32_t*>(gs.rfc + lay.mask);
+    a.flag = reinterpret_cast<int32_t*>(gs.rfc + lay.flag);
     a.ok = ok_dev;
     HIPCHK(launch_gp_refactor(a, s));
     // every kernel reads the hyperparameters from the handle: they change with the factor
@@ -812,20 +816,15 @@ gpmpc_status gpmpc_set_gp_variance_root(gpmpc_handle* h, int32_t gp_id, int32_t 
     if (!h) return fail(GPMPC_ERR_ARG, "null handle");
     if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
     (void)hipSetDevice(h->device);
-    auto drop = [&]() {   // back to the exact variance: root, columns and rank together
-        if (h->gp_vroot[gp_id]) (void)hipFree(h->gp_vroot[gp_id]);
-        h->gp_vroot[gp_id] = nullptr;
-        h->gp_vroot_cols[gp_id] = 0;
-        h->gp_vroot_rank[gp_id] = 0;
-    };
+    GPSlot& gs = h->gp[gp_id];
     if (!R) {
-        drop();
+        gs.drop_root();
         return GPMPC_OK;
     }
-    if (h->gp_npad[gp_id] == 0) return fail(GPMPC_ERR_STATE, "gpmpc_set_gp first");
+    if (h->gp[gp_id].npad == 0) return fail(GPMPC_ERR_STATE, "gpmpc_set_gp first");
     if (n != h->P.gp[gp_id].nv) return fail(GPMPC_ERR_ARG, "root rows must equal the variance GP's training rows");
     if (r < 1 || r > 16 * 16) return fail(GPMPC_ERR_ARG, "root rank must be 1..256");
-    const int npad = h->gp_npad[gp_id], rpad = (r + 15) / 16 * 16;
+    const int npad = h->gp[gp_id].npad, rpad = (r + 15) / 16 * 16;
     std::vector<double> rp((size_t)npad * rpad, 0.0);
     for (int i = 0; i < n; ++i)
         for (int c = 0; c < r; ++c) rp[(size_t)i * rpad + c] = R[(size_t)i * r + c];
@@ -837,10 +836,10 @@ gpmpc_status gpmpc_set_gp_variance_root(gpmpc_handle* h, int32_t gp_id, int32_t 
         if (buf) (void)hipFree(buf);
         return fail(GPMPC_ERR_HIP, std::string("LOVE root upload: ") + hipGetErrorString(e));
     }
-    drop();
-    h->gp_vroot[gp_id] = buf;
-    h->gp_vroot_cols[gp_id] = rpad;
-    h->gp_vroot_rank[gp_id] = r;
+    gs.drop_root();
+    gs.vroot = buf;
+    gs.vroot_cols = rpad;
+    gs.vroot_rank = r;
     return GPMPC_OK;
 }
 
@@ -848,7 +847,7 @@ gpmpc_status gpmpc_use_gp(gpmpc_handle* h, int32_t enabled) {
     if (!h) return fail(GPMPC_ERR_ARG, "null handle");
     if (enabled)
         for (int g = 0; g < h->md.ngp; ++g)
-            if (!h->gp_set[g]) return fail(GPMPC_ERR_STATE, "GP " + std::to_string(g) + " not set");
+            if (!h->gp[g].set) return fail(GPMPC_ERR_STATE, "GP " + std::to_string(g) + " not set");
     if (h->P.use_gp != (enabled ? 1 : 0)) bump_lin(h);
     h->P.use_gp = enabled ? 1 : 0;
     return GPMPC_OK;
@@ -961,7 +960,7 @@ gpmpc_status gpmpc_solve(gpmpc_handle* h, int32_t batch, const double* x0, const
     if (!x0 || !tstep || !u0 || !status) return fail(GPMPC_ERR_ARG, "null output/input");
     if (h->P.tighten && h->P.use_gp)
         for (int g = 0; g < h->md.ngp; ++g)
-            if (!h->gp_linvT[g]) return fail(GPMPC_ERR_STATE, "tightening needs Linv for every GP");
+            if (!h->gp[g].linvT) return fail(GPMPC_ERR_STATE, "tightening needs Linv for every GP");
     (void)hipSetDevice(h->device);
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(order_after_last(h, s));
@@ -1002,10 +1001,10 @@ gpmpc_status gpmpc_solve(gpmpc_handle* h, int32_t batch, const double* x0, const
             a.order = order;
             a.first = first;
             pb.g[g] = P.gp[g];
-            pb.g[g].vroot = h->gp_vroot[g];   // LOVE (fast_pred_var) when a root is set
-            pb.g[g].vroot_cols = h->gp_vroot_cols[g];
-            pb.g[g].vroot_rank = h->gp_vroot_rank[g];
-            pb.npad[g] = h->gp_npad[g];
+            pb.g[g].vroot = h->gp[g].vroot;   // LOVE (fast_pred_var) when a root is set
+            pb.g[g].vroot_cols = h->gp[g].vroot_cols;
+            pb.g[g].vroot_rank = h->gp[g].vroot_rank;
+            pb.npad[g] = h->gp[g].npad;
         }
         return launch_gp_post_batch(pb, true, st);
     };
@@ -1384,9 +1383,9 @@ gpmpc_status gpmpc_get_solution(gpmpc_handle* h, int32_t batch, double* x_dev, d
 gpmpc_status gpmpc_gp_predict(gpmpc_handle* h, int32_t gp_id, const double* Z, int32_t P, double* mean, double* var,
                               int32_t with_noise, void* stream) {
     if (!h) return fail(GPMPC_ERR_ARG, "null handle");
-    if (gp_id < 0 || gp_id >= h->md.ngp || !h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set");
+    if (gp_id < 0 || gp_id >= h->md.ngp || !h->gp[gp_id].set) return fail(GPMPC_ERR_STATE, "GP not set");
     if (P < 0 || (P > 0 && !Z)) return fail(GPMPC_ERR_ARG, "bad points");
-    if (var && !h->gp_linvT[gp_id]) return fail(GPMPC_ERR_STATE, "variance needs Linv");
+    if (var && !h->gp[gp_id].linvT) return fail(GPMPC_ERR_STATE, "variance needs Linv");
     if (P == 0) return GPMPC_OK;
     (void)hipSetDevice(h->device);
     const GPDev& g = h->P.gp[gp_id];
@@ -1410,7 +1409,7 @@ gpmpc_status gpmpc_gp_predict(gpmpc_handle* h, int32_t gp_id, const double* Z, i
     if (var) {
         a.mean = nullptr;
         a.var = var;
-        HIPCHK(launch_gp_post(g, h->gp_npad[gp_id], a, false, (hipStream_t)stream, h->var_trim ? 0 : 1));
+        HIPCHK(launch_gp_post(g, h->gp[gp_id].npad, a, false, (hipStream_t)stream, h->var_trim ? 0 : 1));
     }
     return GPMPC_OK;
 }
@@ -1418,7 +1417,7 @@ gpmpc_status gpmpc_gp_predict(gpmpc_handle* h, int32_t gp_id, const double* Z, i
 gpmpc_status gpmpc_gp_mean_grad(gpmpc_handle* h, int32_t gp_id, const double* Z, int32_t P, double* mean,
                                 double* grad, void* stream) {
     if (!h) return fail(GPMPC_ERR_ARG, "null handle");
-    if (gp_id < 0 || gp_id >= h->md.ngp || !h->gp_set[gp_id]) return fail(GPMPC_ERR_STATE, "GP not set");
+    if (gp_id < 0 || gp_id >= h->md.ngp || !h->gp[gp_id].set) return fail(GPMPC_ERR_STATE, "GP not set");
     if (P < 0 || (P > 0 && !Z)) return fail(GPMPC_ERR_ARG, "bad points");
     if (P == 0) return GPMPC_OK;
     (void)hipSetDevice(h->device);

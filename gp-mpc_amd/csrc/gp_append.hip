@@ -29,11 +29,9 @@
 //
 // The tile pack stays centred on the xbar gpmpc_set_gp computed: the centring is algebraically exact
 // for any xbar and only conditions the exponent.
-#include "gpmpc_common.h"
+#include "gp_tile.h"
 
 namespace gpmpc {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kAppWaves = 4;   // column tiles per workgroup (one wave each, no LDS)
 
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(64 * kAppWaves) void gp_append_w_kernel(GPAppend a)
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {   // four independent exps
             const double d0 = rw[ks].x - z[0], d1 = rw[ks].y - z[1], d2 = rw[ks].z - z[2];
-            const double e = a.sf2 * exp_rbf(c * fma(d0, d0, fma(d1, d1, d2 * d2)));
+            const double e = rbf_raw(c, a.sf2, d0, d1, d2);
             kv[ks] = pvalid ? e : 0.0;
         }
 #pragma unroll
@@ -108,54 +106,22 @@ __global__ __launch_bounds__(64) void gp_append_chol_kernel(GPAppend a) {
         fin = fin && isfinite(mu);
         res[lane] = lane < m ? yv - mu : 0.0;
     }
-    // Gram matrix G = W^T W over the old rows: lane (lc, kq) takes columns 16s + 4kq + j of row lc
-    // (the K order of an MFMA sum is free as long as both operands agree: here they are one register)
-    f64x4 g[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) g[j] = f64x4{0.0, 0.0, 0.0, 0.0};
-    const double* wrow = a.wt + (size_t)lc * a.ldw + 4 * kq;
-    for (int s = 0; s < nt; ++s) {
-        const double4 w = *reinterpret_cast<const double4*>(wrow + 16 * s);
-        g[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.x, w.x, g[0], 0, 0, 0);
-        g[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.y, w.y, g[1], 0, 0, 0);
-        g[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.z, w.z, g[2], 0, 0, 0);
-        g[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.w, w.w, g[3], 0, 0, 0);
-    }
+    // Gram matrix G = W^T W over the old rows
+    const f64x4 gw = gram16(a.wt + (size_t)lc * a.ldw + 4 * kq, nt);
     __syncthreads();
     const double c = -0.5 * a.inv_ell2;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int p = kq + 4 * r, q = lc;   // G[p][q]
-        const double gv = (g[0][r] + g[1][r]) + (g[2][r] + g[3][r]);
         const double d0 = xb[p][0] - xb[q][0], d1 = xb[p][1] - xb[q][1], d2 = xb[p][2] - xb[q][2];
-        const double kbb = a.sf2 * exp_rbf(c * fma(d0, d0, fma(d1, d1, d2 * d2))) + (p == q ? a.sn2 : 0.0);
-        S[p][q] = (p < m && q < m) ? kbb - gv : (p == q ? 1.0 : 0.0);
+        const double kbb = rbf_raw(c, a.sf2, d0, d1, d2) + (p == q ? a.sn2 : 0.0);
+        S[p][q] = (p < m && q < m) ? kbb - gw[r] : (p == q ? 1.0 : 0.0);
         Li[p][q] = 0.0;
     }
-    bool ok = __all(fin);
-    // Cholesky factor in place (lower triangle), lane = row
-    for (int j = 0; j < 16; ++j) {
-        __syncthreads();
-        double s = 0.0;
-        if (lane < 16 && lane >= j) {
-            s = S[lane][j];
-            for (int k = 0; k < j; ++k) s = fma(-S[lane][k], S[j][k], s);
-        }
-        const double piv = __shfl(s, j);
-        const bool good = isfinite(piv) && piv > 0.0;
-        ok = ok && good;
-        const double ljj = good ? sqrt(piv) : 1.0;
-        if (lane < 16 && lane >= j) S[lane][j] = (lane == j) ? ljj : s / ljj;
-    }
     __syncthreads();
-    // L_b^-1 by forward substitution, lane = column
-    if (lane < 16) {
-        for (int i = lane; i < 16; ++i) {
-            double s = (i == lane) ? 1.0 : 0.0;
-            for (int k = lane; k < i; ++k) s = fma(-S[i][k], Li[k][lane], s);
-            Li[i][lane] = s / S[i][i];
-        }
-    }
+    bool ok = __all(fin);
+    ok = chol16<true>(S, nullptr, lane) && ok;   // (measured against the LDS pivot: profiles/r13)
+    inv_lower16(S, Li, lane);   // L_b^-1
     __syncthreads();
     if (lane < 16) {   // beta = L_b^-1 (y_b - mean)
         double s = 0.0;
@@ -185,26 +151,17 @@ __global__ __launch_bounds__(64) void gp_append_chol_kernel(GPAppend a) {
     if (lane < 16) a.beta[lane] = bet[lane];
     if (lane < m) {
         const int i = a.n0 + lane;
-        const int t = i / 16, rr = i % 16, grp = rr % 4, q = rr / 4;   // (the lane order gpmpc_set_gp documents)
-        double xc[3], sq = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            xc[k] = (k < a.d) ? xb[lane][k] - a.xbar[k] : 0.0;
-            sq += xc[k] * xc[k];
-        }
+        const TileSlot slot = tile_slot(i);
+        double xc[3];
+        tile_centre(xc, xb[lane][0], xb[lane][1], xb[lane][2], a.xbar, a.d);
         const double al = gam[lane];
         double* row = a.rows + (size_t)i * 4;
         row[0] = xb[lane][0];
         row[1] = xb[lane][1];
         row[2] = xb[lane][2];
         row[3] = al;
-        double* tx = a.tX + (size_t)t * 64 + rr * 4;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) tx[k] = (k < a.d) ? a.inv_ell2 * xc[k] : 0.0;
-        tx[3] = c * sq;
-        const double wv[4] = {al, al * xc[0], al * xc[1], al * xc[2]};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a.tW[(size_t)t * 64 + (grp * 4 + j) * 4 + q] = wv[j];
+        tile_write_x(a.tX, slot, xc, a.inv_ell2, c);
+        tile_write_w(a.tW, slot, al, xc);
     }
 }
 
@@ -248,12 +205,9 @@ __global__ __launch_bounds__(64 * kAppWaves) void gp_append_r_kernel(GPAppend a)
         const double4 rw = reinterpret_cast<const double4*>(a.rows)[i];
         const double al = rw.w + da;
         a.rows[(size_t)i * 4 + 3] = al;
-        const double xc[3] = {a.d > 0 ? rw.x - a.xbar[0] : 0.0, a.d > 1 ? rw.y - a.xbar[1] : 0.0,
-                              a.d > 2 ? rw.z - a.xbar[2] : 0.0};
-        const int grp = lc % 4, q = lc / 4;
-        const double wv[4] = {al, al * xc[0], al * xc[1], al * xc[2]};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a.tW[(size_t)t * 64 + (grp * 4 + j) * 4 + q] = wv[j];
+        double xc[3];
+        tile_centre(xc, rw.x, rw.y, rw.z, a.xbar, a.d);
+        tile_write_w(a.tW, tile_slot(t, lc), al, xc);
     }
 }
 
@@ -262,14 +216,10 @@ hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream) {
         return hipErrorInvalidValue;
     const int nt = (a.n0 + 15) / 16;
     const int blocks = (nt + kAppWaves - 1) / kAppWaves;
-    hipLaunchKernelGGL(gp_append_w_kernel, dim3(blocks), dim3(64 * kAppWaves), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gp_append_chol_kernel, dim3(1), dim3(64), 0, stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gp_append_r_kernel, dim3(blocks), dim3(64 * kAppWaves), 0, stream, a);
-    return hipGetLastError();
+    GP_LAUNCH(gp_append_w_kernel, dim3(blocks), dim3(64 * kAppWaves), stream, a);
+    GP_LAUNCH(gp_append_chol_kernel, dim3(1), dim3(64), stream, a);
+    GP_LAUNCH(gp_append_r_kernel, dim3(blocks), dim3(64 * kAppWaves), stream, a);
+    return hipSuccess;
 }
 
 }  // namespace gpmpc

@@ -43,48 +43,11 @@
 // contents are unspecified (every access stays in bounds whatever the values).
 //
 // The tile pack stays centred on the xbar gpmpc_set_gp computed (tX is moved, tW rewritten).
-#include "gpmpc_common.h"
+#include "gp_tile.h"
 
 namespace gpmpc {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kDropWaves = 4;   // column tiles per workgroup of the apply kernel (one wave each, no LDS)
-
-// Cholesky factor of the 16 x 16 matrix S in place (lower triangle), thread = row; every thread of the
-// workgroup calls it (tmp: 16 doubles of LDS).  Returns whether every pivot was finite and positive
-// (the same value in every thread); a bad pivot is replaced by 1.
-__device__ inline bool chol16(double (*S)[17], double* tmp, int tid) {
-    bool ok = true;
-    for (int j = 0; j < 16; ++j) {
-        double s = 0.0;
-        if (tid < 16 && tid >= j) {
-            s = S[tid][j];
-            for (int k = 0; k < j; ++k) s = fma(-S[tid][k], S[j][k], s);
-            if (tid == j) tmp[0] = s;
-        }
-        __syncthreads();
-        const double piv = tmp[0];
-        const bool good = isfinite(piv) && piv > 0.0;
-        ok = ok && good;
-        const double ljj = good ? sqrt(piv) : 1.0;
-        if (tid < 16 && tid >= j) S[tid][j] = (tid == j) ? ljj : s / ljj;
-        __syncthreads();
-    }
-    return ok;
-}
-
-// Inverse of the lower-triangular 16 x 16 matrix S into Li (zero above the diagonal on entry),
-// thread = column
-__device__ inline void inv_lower16(double (*S)[17], double (*Li)[17], int tid) {
-    if (tid < 16) {
-        for (int i = tid; i < 16; ++i) {
-            double s = (i == tid) ? 1.0 : 0.0;
-            for (int k = tid; k < i; ++k) s = fma(-S[i][k], Li[k][tid], s);
-            Li[i][tid] = s / S[i][i];
-        }
-    }
-}
 
 // One workgroup of 256: L11, P11 and g on its first wave, then V^T and M21 g over all columns.
 __global__ __launch_bounds__(256) void gp_drop_head_kernel(GPDrop a) {
@@ -103,25 +66,12 @@ __global__ __launch_bounds__(256) void gp_drop_head_kernel(GPDrop a) {
         Li[p][q] = 0.0;
     }
     if (wave == 0) {
-        // P11 = Gram matrix of rows 0 .. m-1 of linvT: lane (lc, kq) takes columns 16s + 4kq + j of
-        // row lc (both MFMA operands are one register, so the K order is free)
-        f64x4 g[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) g[j] = f64x4{0.0, 0.0, 0.0, 0.0};
-        const double* row = a.src + (size_t)lc * a.npad0 + 4 * kq;
-        const bool live = lc < m;
-        for (int s = 0; s < a.npad0 / 16; ++s) {
-            double4 w = *reinterpret_cast<const double4*>(row + 16 * s);
-            if (!live) w = double4{0.0, 0.0, 0.0, 0.0};
-            g[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.x, w.x, g[0], 0, 0, 0);
-            g[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.y, w.y, g[1], 0, 0, 0);
-            g[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.z, w.z, g[2], 0, 0, 0);
-            g[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.w, w.w, g[3], 0, 0, 0);
-        }
+        // P11 = Gram matrix of rows 0 .. m-1 of linvT
+        const f64x4 g = gram16(a.src + (size_t)lc * a.npad0 + 4 * kq, a.npad0 / 16, lc < m);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int p = kq + 4 * r, q = lc;
-            double v = (g[0][r] + g[1][r]) + (g[2][r] + g[3][r]);
+            double v = g[r];
             if (p >= m || q >= m) v = (p == q) ? 1.0 : 0.0;
             if (p == q && v == 0.0) v = 1.0;
             P[p][q] = v;
@@ -170,21 +120,11 @@ __global__ __launch_bounds__(64) void gp_drop_tile_kernel(GPDrop a) {
     __shared__ double G[16][17], VT[16][17], E[16][17], F[16][17], D[16][17], tmp[16];
     const int lane = threadIdx.x, T = blockIdx.x;
     const int lc = lane & 15, kq = lane >> 4;
-    f64x4 g[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) g[j] = f64x4{0.0, 0.0, 0.0, 0.0};
-    const double* vrow = a.vt + (size_t)lc * a.ldv + 4 * kq;
-    for (int s = 0; s < T; ++s) {   // the kept rows before the tile
-        const double4 w = *reinterpret_cast<const double4*>(vrow + 16 * s);
-        g[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.x, w.x, g[0], 0, 0, 0);
-        g[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.y, w.y, g[1], 0, 0, 0);
-        g[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.z, w.z, g[2], 0, 0, 0);
-        g[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(w.w, w.w, g[3], 0, 0, 0);
-    }
+    const f64x4 g = gram16(a.vt + (size_t)lc * a.ldv + 4 * kq, T);   // over the kept rows before the tile
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int p = kq + 4 * r, q = lc;
-        G[p][q] = (g[0][r] + g[1][r]) + (g[2][r] + g[3][r]) + (p == q ? 1.0 : 0.0);
+        G[p][q] = g[r] + (p == q ? 1.0 : 0.0);
         VT[p][q] = a.vt[(size_t)p * a.ldv + 16 * T + q];   // V^T[p][row q of the tile]
         D[p][q] = 0.0;
     }
@@ -282,12 +222,9 @@ __global__ __launch_bounds__(64 * kDropWaves) void gp_drop_apply_kernel(GPDrop a
         const double al = cok ? rw.w - da : 0.0;
         reinterpret_cast<double4*>(a.srows)[c] = double4{rw.x, rw.y, rw.z, al};
         reinterpret_cast<double4*>(a.stX)[c] = tx;
-        const double xc[3] = {a.d > 0 ? rw.x - a.xbar[0] : 0.0, a.d > 1 ? rw.y - a.xbar[1] : 0.0,
-                              a.d > 2 ? rw.z - a.xbar[2] : 0.0};
-        const int grp = lc % 4, q = lc / 4;
-        const double wv[4] = {al, al * xc[0], al * xc[1], al * xc[2]};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a.stW[(size_t)J * 64 + (grp * 4 + j) * 4 + q] = cok ? wv[j] : 0.0;
+        double xc[3];
+        tile_centre(xc, rw.x, rw.y, rw.z, a.xbar, a.d);
+        tile_write_w(a.stW, tile_slot(J, lc), al, xc, cok);
     }
 }
 
@@ -296,15 +233,10 @@ hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream) {
         a.n0 - a.m > a.npad1 || a.npad1 > a.npad0 || a.ldv < a.npad1)
         return hipErrorInvalidValue;
     const int nt = a.npad1 / 16;
-    hipLaunchKernelGGL(gp_drop_head_kernel, dim3(1), dim3(256), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gp_drop_tile_kernel, dim3(nt), dim3(64), 0, stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const int blocks = (nt + kDropWaves - 1) / kDropWaves;
-    hipLaunchKernelGGL(gp_drop_apply_kernel, dim3(blocks), dim3(64 * kDropWaves), 0, stream, a);
-    return hipGetLastError();
+    GP_LAUNCH(gp_drop_head_kernel, dim3(1), dim3(256), stream, a);
+    GP_LAUNCH(gp_drop_tile_kernel, dim3(nt), dim3(64), stream, a);
+    GP_LAUNCH(gp_drop_apply_kernel, dim3((nt + kDropWaves - 1) / kDropWaves), dim3(64 * kDropWaves), stream, a);
+    return hipSuccess;
 }
 
 }  // namespace gpmpc

@@ -39,12 +39,10 @@
 // Guard.  The status is 1 when every live target is finite and every pivot finite and positive (a
 // bad pivot is replaced by 1); otherwise 0 and the GP's contents are unspecified.  Every access stays
 // in bounds whatever the values.
-#include "gpmpc_common.h"
+#include "gp_tile.h"
 #include <algorithm>
 
 namespace gpmpc {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kRefWaves = 4;   // tiles per workgroup (one wave each)
 
@@ -77,7 +75,7 @@ __global__ __launch_bounds__(256) void gp_refactor_build_kernel(GPRefactor a) {
     const double4 xi = rows[i], xj = rows[j];
     const double d0 = xi.x - xj.x, d1 = xi.y - xj.y, d2 = xi.z - xj.z;
     const double c = -0.5 * a.inv_ell2;
-    double v = a.sf2 * exp_rbf(c * fma(d0, d0, fma(d1, d1, d2 * d2)));
+    double v = rbf_raw(c, a.sf2, d0, d1, d2);
     if (i == j) v = a.sf2 + a.sn2;
     if (a.mask[i] || a.mask[j]) v = (i == j) ? 1.0 : 0.0;
     a.A[(size_t)i * a.npad + j] = v;
@@ -252,22 +250,11 @@ __global__ __launch_bounds__(64 * kRefWaves) void gp_refactor_alpha_kernel(GPRef
     const double4 rw = reinterpret_cast<const double4*>(a.rows)[j];
     const double al = live ? s : 0.0;
     a.rows[(size_t)j * 4 + 3] = al;
-    const int t = j / 16, rr = j % 16, grp = rr % 4, q = rr / 4;   // (the lane order gpmpc_set_gp documents)
-    const double xr[3] = {rw.x, rw.y, rw.z};
-    double xc[3], sq = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        xc[k] = (k < a.d && live) ? xr[k] - a.xbar[k] : 0.0;
-        sq += xc[k] * xc[k];
-    }
-    const double c = -0.5 * a.inv_ell2;
-    double* tx = a.tX + (size_t)t * 64 + rr * 4;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) tx[k] = a.inv_ell2 * xc[k];
-    tx[3] = live ? c * sq : 0.0;
-    const double wv[4] = {al, al * xc[0], al * xc[1], al * xc[2]};
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) a.tW[(size_t)t * 64 + (grp * 4 + jj) * 4 + q] = wv[jj];
+    const TileSlot slot = tile_slot(j);
+    double xc[3];
+    tile_centre(xc, rw.x, rw.y, rw.z, a.xbar, a.d, live);
+    tile_write_x(a.tX, slot, xc, a.inv_ell2, -0.5 * a.inv_ell2, live);
+    tile_write_w(a.tW, slot, al, xc);
 }
 
 hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream) {
@@ -275,28 +262,17 @@ hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream) {
     const int nt = a.npad / 16, nb = (a.npad + 255) / 256, tb = (nt + kRefWaves - 1) / kRefWaves;
     hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.flag), 1, 1, stream);   // the status starts at 1
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gp_refactor_mask_kernel, dim3(nb), dim3(256), 0, stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gp_refactor_build_kernel, dim3(nt, nt), dim3(256), 0, stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    GP_LAUNCH(gp_refactor_mask_kernel, dim3(nb), dim3(256), stream, a);
+    GP_LAUNCH(gp_refactor_build_kernel, dim3(nt, nt), dim3(256), stream, a);
     for (int k = 0; k < nt; ++k) {
         const int below = nt - k - 1;
-        hipLaunchKernelGGL(gp_refactor_panel_kernel, dim3(std::max(1, (below + kRefWaves - 1) / kRefWaves)),
-                           dim3(64 * kRefWaves), 0, stream, a, k);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(gp_refactor_update_kernel, dim3(tb, nt - k), dim3(64 * kRefWaves), 0, stream, a, k);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        GP_LAUNCH(gp_refactor_panel_kernel, dim3(std::max(1, (below + kRefWaves - 1) / kRefWaves)), dim3(64 * kRefWaves),
+                  stream, a, k);
+        GP_LAUNCH(gp_refactor_update_kernel, dim3(tb, nt - k), dim3(64 * kRefWaves), stream, a, k);
     }
-    hipLaunchKernelGGL(gp_refactor_w_kernel, dim3((a.npad + 63) / 64), dim3(1024), 0, stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gp_refactor_alpha_kernel, dim3((a.npad + kRefWaves - 1) / kRefWaves), dim3(64 * kRefWaves), 0,
-                       stream, a);
-    return hipGetLastError();
+    GP_LAUNCH(gp_refactor_w_kernel, dim3((a.npad + 63) / 64), dim3(1024), stream, a);
+    GP_LAUNCH(gp_refactor_alpha_kernel, dim3((a.npad + kRefWaves - 1) / kRefWaves), dim3(64 * kRefWaves), stream, a);
+    return hipSuccess;
 }
 
 }  // namespace gpmpc

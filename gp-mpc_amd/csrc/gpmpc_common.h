@@ -352,7 +352,8 @@ struct GPRefactor {
     int32_t* ok;          // the caller's status word, may be null
 };
 
-// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip, gp_refactor.hip).
+// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip, gp_refactor.hip; what the last three
+// share, the tile pack's layout included, is in gp_tile.h).
 hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream);
 hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream);
 hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream);

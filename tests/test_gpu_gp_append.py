@@ -29,25 +29,23 @@ import numpy as np
 import pytest
 
 import gp_ref as R
+import gp_update_util as U
 from gp_append_ref import MARGIN, reference, worst_ratio
-from helpers import initial_states, lqr, problem, product_gps
+from gp_update_util import REFKEY, SF2, SN2
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not R.have_extended(), reason="np.longdouble is not wider than float64")]
 
-SF2, SN2 = 1.0, 1e-3
 NPTS = 64
-GUARD = 64
-SENTINEL = -7.25e77
 RATIOS: dict = {}
+_torch = U.gpu_torch
+_gp_objects = U.gp_objects
+_outputs = U.outputs
+_upload = U.upload
 
 
-def _torch():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
+def _solver(key):
+    return U.solver(__name__, key)
 
 
 def _reference(X, y, ell, Z):
@@ -67,55 +65,6 @@ def _data(n, seed):
     return out
 
 
-# ---------------------------------------------------------------------------- device side
-_SOLVERS: dict = {}
-
-
-def _solver(key, H=5, B=2, **kw):
-    _torch()
-    from gpmpc.models import get_spec
-    from gpmpc.solver import BatchSolver
-
-    if key not in _SOLVERS:
-        _SOLVERS[key] = BatchSolver(get_spec("quad2d"), H, B, **kw)
-    return _SOLVERS[key]
-
-
-def _gp_objects(data, rows):
-    """GaussianProcess per GP on the given rows (an index array or slice) of the case's data."""
-    torch = _torch()
-    from gpmpc.gp import GaussianProcess
-
-    gps = []
-    for dg in data:
-        gp = GaussianProcess(torch.tensor(dg["X"][rows]), torch.tensor(dg["y"][rows]))
-        gp.set_hyperparameters(dg["ell"], SF2, SN2)
-        gps.append(gp)
-    return gps
-
-
-def _guarded(P, dtype=None):
-    torch = _torch()
-    if dtype is torch.int32:
-        t = torch.full((P + GUARD,), -77, dtype=torch.int32, device="cuda")
-        t[P:] = -99
-        return t
-    t = torch.full((P + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
-    t[P:] = SENTINEL
-    return t
-
-
-def _read(t, P, what):
-    a = t.cpu().numpy()
-    if a.dtype == np.int32:
-        assert (a[P:] == -99).all(), f"{what}: wrote past the end of the output"
-        assert (a[:P] != -77).all(), f"{what}: output not written"
-        return a[:P].copy()
-    assert (a[P:] == SENTINEL).all(), f"{what}: wrote past the end of the output"
-    assert not np.isnan(a[:P]).any(), f"{what}: {int(np.isnan(a[:P]).sum())} of {P} outputs not written"
-    return a[:P].copy()
-
-
 def _append(s, g, X, y, what):
     """gpmpc_gp_append of (X, y) to GP g with a guarded status array; returns the flags (host)."""
     torch = _torch()
@@ -124,28 +73,10 @@ def _append(s, g, X, y, what):
     Xt = torch.tensor(np.ascontiguousarray(X, dtype=np.float64).reshape(len(y), -1), device="cuda")
     yt = torch.tensor(np.ascontiguousarray(y, dtype=np.float64), device="cuda")
     nb = (len(y) + 15) // 16
-    fl = _guarded(nb, torch.int32)
+    fl = U.guarded(nb, torch.int32)
     _lib.check(s.lib.gpmpc_gp_append(s._h, g, len(y), Xt.data_ptr(), yt.data_ptr(), fl.data_ptr(), s._stream()))
     torch.cuda.synchronize()
-    return _read(fl, nb, what + " flags")
-
-
-def _outputs(s, g, Z, what):
-    """gp_predict mean / predictive variance and gp_mean_grad mean / gradient at Z, guarded."""
-    torch = _torch()
-    from gpmpc import _lib
-
-    P, d = Z.shape
-    Zt = torch.tensor(np.ascontiguousarray(Z), device="cuda")
-    mb, vb, gm, gg = _guarded(P), _guarded(P), _guarded(P), _guarded(P * d)
-    s.gp_predict(g, Zt, with_noise=True, mean=mb, var=vb)
-    _lib.check(s.lib.gpmpc_gp_mean_grad(s._h, g, Zt.data_ptr(), P, gm.data_ptr(), gg.data_ptr(), s._stream()))
-    torch.cuda.synchronize()
-    return dict(mean=_read(mb, P, what + " mean"), var=_read(vb, P, what + " var"),
-                tmean=_read(gm, P, what + " tile mean"), grad=_read(gg, P * d, what + " grad").reshape(P, d))
-
-
-REFKEY = dict(mean="mean", var="var", tmean="mean", grad="grad")
+    return U.read(fl, nb, what + " flags")
 
 
 def _compare(case, g, app, full, ref):
@@ -156,13 +87,6 @@ def _compare(case, g, app, full, ref):
         print(f"[gp-append] {case} gp{g} {q}: e_app {e_app:.3e} e_full {e_full:.3e} ratio {ratio:.3f}")
     for q in ("mean", "var", "tmean", "grad"):
         assert RATIOS[(case, g, q)] <= MARGIN, (case, g, q, RATIOS[(case, g, q)])
-
-
-def _upload(s, data, rows, capacity=None):
-    s.set_gps(_gp_objects(data, rows))
-    if capacity is not None:
-        for g in range(2):
-            s.reserve_gp(g, capacity)
 
 
 CASES = [("inside a tile", 5, (3,)), ("filling a tile exactly", 13, (3,)), ("crossing a tile boundary", 14, (5,)),
@@ -256,23 +180,8 @@ def test_reserved_capacity_is_not_overrun():
 
 def _refused(s, g, dg, code, cause, var=True):
     """append_gp of one row is refused with `code` and a message naming `cause`; predictions bit-identical."""
-    torch = _torch()
-    from gpmpc import _lib
-
-    Zt = torch.tensor(dg["Z"], device="cuda")
-
-    def snap():
-        m, v = s.gp_predict(g, Zt, with_noise=True, var=var)
-        tm, tg = s.gp_mean_grad(g, Zt)
-        torch.cuda.synchronize()
-        return [t.cpu().numpy() for t in (m, v, tm, tg) if t is not None]
-
-    before, size = snap(), s.gp_size(g)
-    with pytest.raises(_lib.GPMPCError, match=rf"error {code}: .*{cause}"):
+    with U.refused(s, g, dg, code, cause, var):
         s.append_gp(g, dg["X"][:1], dg["y"][:1])
-    assert s.gp_size(g) == size
-    after = snap()
-    assert len(before) == len(after) and all(np.array_equal(a, b) for a, b in zip(before, after))
 
 
 def test_refusals_leave_the_gp_unchanged():
@@ -332,66 +241,23 @@ def test_tightening_and_solve_after_append():
     Three closed-loop steps each (solve, plant_step): identical statuses; x, u and variance() agree
     within 1e-6 (1 + |.|).  A step of handle A that follows an append computes its first
     linearisation (stats slot 9 advances by sqp_iter + 1, against sqp_iter for a cache hit)."""
-    torch = _torch()
-    from gpmpc.solver import BatchSolver
-
-    H, B, tol = 5, 8, 1e-9
-    spec, data, hyp = problem("quad2d", 57)
-    mats = lqr(spec)
-    traj = spec.reference_trajectory()
-    x0, phase = initial_states(spec, traj, B)
-
-    def handle(rows):
-        s = BatchSolver(spec, H, B, tol=tol, qp_tol=1e-11, qp_max_iter=100)
-        s.set_gps(product_gps([(X[:rows], y[:rows]) for X, y in data], hyp))
-        s.set_tightening(True, 0.95, *mats)
-        s.reset(reset_iterate=True)
-        return s
+    loop = U.ClosedLoop(57)
+    data, hyp = loop.data, loop.hyp
 
     def append(s, lo, hi):
         for g, (X, y) in enumerate(data):
             assert s.append_gp(g, X[lo:hi], y[lo:hi]).cpu().tolist() == [1]
 
-    sa, sb = handle(30), handle(48)
-    stats = torch.zeros(B, sa.STATS_SLOTS, dtype=torch.int64, device="cuda")
-    sa.set_stats(stats)
+    sa, sb = (loop.handle([(X[:rows], y[:rows]) for X, y in data], hyp) for rows in (30, 48))
+    loop.start(sa, sb)
     for g in range(2):
         sa.reserve_gp(g, 57)
     append(sa, 30, 39)
     append(sa, 39, 48)
     assert [sa.gp_size(g) for g in range(2)] == [(48, 57)] * 2
-    obs = [torch.tensor(x0, device="cuda"), torch.tensor(x0, device="cuda")]
-    ts = [torch.tensor(phase, dtype=torch.int32, device="cuda") for _ in range(2)]
-    lin_prev = stats[:, 9].clone()
-
-    def step(i, s):
-        u = s.solve(obs[i], ts[i].clone())
-        out = dict(st=s.status.cpu().numpy(), it=s.sqp_iter.cpu().numpy())
-        out["x"], out["u"], _ = (t.cpu().numpy() for t in s.solution())
-        obs[i] = s.plant_step(obs[i], u.clone(), ts[i])
-        return out
-
-    def close(a, b):
-        return float((np.abs(a - b) / (1 + np.abs(b))).max())
-
-    for k in range(3):
-        ra, rb = step(0, sa), step(1, sb)
-        np.testing.assert_array_equal(ra["st"], rb["st"])
-        assert np.isin(ra["st"], (0, 2)).all(), ra["st"]
-        assert close(ra["x"], rb["x"]) <= 1e-6 and close(ra["u"], rb["u"]) <= 1e-6, (k, close(ra["x"], rb["x"]))
-        if k > 0:   # (the first step after a reset runs no variance launch)
-            va, vb = sa.variance().cpu().numpy(), sb.variance().cpu().numpy()
-            assert close(va, vb) <= 1e-6, (k, close(va, vb))
-        lin = stats[:, 9].clone()
-        d = (lin - lin_prev).cpu().numpy()
-        # step 0 follows the appends (and the reset): no cached rows; steps 1, 2 read the cache
-        np.testing.assert_array_equal(d, ra["it"] + (1 if k == 0 else 0))
-        lin_prev = lin
+    loop.three_steps()
     append(sa, 48, 57)
-    ra = step(0, sa)
-    d = (stats[:, 9] - lin_prev).cpu().numpy()
-    assert (d > 0).all()
-    np.testing.assert_array_equal(d, ra["it"] + 1)   # the cache served nothing computed with the old model
+    loop.step_after_update()
 
 
 def test_zz_report_ratios():

@@ -24,82 +24,27 @@ import pytest
 
 import gp_drop_ref as D
 import gp_ref as R
+import gp_update_util as U
 from gp_append_ref import reference, worst_ratio
-from helpers import initial_states, lqr, problem, product_gps
+from gp_update_util import QUANT, REFKEY, SF2, SN2
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not R.have_extended(), reason="np.longdouble is not wider than float64")]
 
-SF2, SN2, NPTS = D.SF2, D.SN2, D.NPTS
-GUARD = 64
-SENTINEL = -7.25e77
 RATIOS: dict = {}
+_torch = U.gpu_torch
+_gp_objects = U.gp_objects
+_nan_block = U.nan_block
+_outputs = U.outputs
+_upload = U.upload
 
 
-def _torch():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
+def _solver(key):
+    return U.solver(__name__, key)
 
 
 def _reference(dg, rows, Z=None):
     return reference(dg["X"][rows], dg["y"][rows], dg["ell"], SF2, SN2, dg["Z"] if Z is None else Z)
-
-
-_SOLVERS: dict = {}
-
-
-def _solver(key, H=5, B=2, **kw):
-    _torch()
-    from gpmpc.models import get_spec
-    from gpmpc.solver import BatchSolver
-
-    if key not in _SOLVERS:
-        _SOLVERS[key] = BatchSolver(get_spec("quad2d"), H, B, **kw)
-    return _SOLVERS[key]
-
-
-def _gp_objects(data, rows):
-    torch = _torch()
-    from gpmpc.gp import GaussianProcess
-
-    gps = []
-    for dg in data:
-        gp = GaussianProcess(torch.tensor(dg["X"][rows]), torch.tensor(dg["y"][rows]))
-        gp.set_hyperparameters(dg["ell"], SF2, SN2)
-        gps.append(gp)
-    return gps
-
-
-def _upload(s, data, rows, capacity=None):
-    s.set_gps(_gp_objects(data, rows))
-    if capacity is not None:
-        for g in range(2):
-            s.reserve_gp(g, capacity)
-
-
-def _guarded(P, dtype=None):
-    torch = _torch()
-    if dtype is torch.int32:
-        t = torch.full((P + GUARD,), -77, dtype=torch.int32, device="cuda")
-        t[P:] = -99
-        return t
-    t = torch.full((P + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
-    t[P:] = SENTINEL
-    return t
-
-
-def _read(t, P, what):
-    a = t.cpu().numpy()
-    if a.dtype == np.int32:
-        assert (a[P:] == -99).all(), f"{what}: wrote past the end of the output"
-        assert (a[:P] != -77).all(), f"{what}: output not written"
-        return a[:P].copy()
-    assert (a[P:] == SENTINEL).all(), f"{what}: wrote past the end of the output"
-    assert not np.isnan(a[:P]).any(), f"{what}: {int(np.isnan(a[:P]).sum())} of {P} outputs not written"
-    return a[:P].copy()
 
 
 def _drop(s, g, m, what):
@@ -108,29 +53,10 @@ def _drop(s, g, m, what):
     from gpmpc import _lib
 
     nb = (m + 15) // 16
-    fl = _guarded(nb, torch.int32)
+    fl = U.guarded(nb, torch.int32)
     _lib.check(s.lib.gpmpc_gp_drop_oldest(s._h, g, m, fl.data_ptr(), s._stream()))
     torch.cuda.synchronize()
-    return _read(fl, nb, what + " flags").tolist()
-
-
-def _outputs(s, g, Z, what):
-    """gp_predict mean / predictive variance and gp_mean_grad mean / gradient at Z, guarded."""
-    torch = _torch()
-    from gpmpc import _lib
-
-    P, d = Z.shape
-    Zt = torch.tensor(np.ascontiguousarray(Z), device="cuda")
-    mb, vb, gm, gg = _guarded(P), _guarded(P), _guarded(P), _guarded(P * d)
-    s.gp_predict(g, Zt, with_noise=True, mean=mb, var=vb)
-    _lib.check(s.lib.gpmpc_gp_mean_grad(s._h, g, Zt.data_ptr(), P, gm.data_ptr(), gg.data_ptr(), s._stream()))
-    torch.cuda.synchronize()
-    return dict(mean=_read(mb, P, what + " mean"), var=_read(vb, P, what + " var"),
-                tmean=_read(gm, P, what + " tile mean"), grad=_read(gg, P * d, what + " grad").reshape(P, d))
-
-
-REFKEY = dict(mean="mean", var="var", tmean="mean", grad="grad")
-QUANT = ("mean", "var", "tmean", "grad")
+    return U.read(fl, nb, what + " flags").tolist()
 
 
 def _compare(case, g, got, full, ref, n_kept):
@@ -164,13 +90,6 @@ def test_drop_matches_full_recompute(case, n, drops):
         got = _outputs(sa, g, dg["Z"], f"{case} dropped gp{g}")
         full = _outputs(sb, g, dg["Z"], f"{case} full gp{g}")
         _compare(case, g, got, full, refs[g], left)
-
-
-def _nan_block(s, g, d, m, seed):
-    rng = np.random.default_rng(seed)
-    Xb, yb = rng.uniform(-1, 1, (m, d)), rng.uniform(0.5, 1.5, m)
-    yb[m // 2] = np.nan
-    assert s.append_gp(g, Xb, yb).cpu().tolist() == [0]
 
 
 def test_inert_rows_are_dropped_and_kept():
@@ -252,23 +171,8 @@ def test_two_handles_end_bit_identical():
 
 def _refused(s, g, dg, m, code, cause, var=True):
     """drop_gp of m rows is refused with `code` and a message naming `cause`; size and predictions unchanged."""
-    torch = _torch()
-    from gpmpc import _lib
-
-    Zt = torch.tensor(dg["Z"], device="cuda")
-
-    def snap():
-        mu, v = s.gp_predict(g, Zt, with_noise=True, var=var)
-        tm, tg = s.gp_mean_grad(g, Zt)
-        torch.cuda.synchronize()
-        return [t.cpu().numpy() for t in (mu, v, tm, tg) if t is not None]
-
-    before, size = snap(), s.gp_size(g)
-    with pytest.raises(_lib.GPMPCError, match=rf"error {code}: .*{cause}"):
+    with U.refused(s, g, dg, code, cause, var):
         s.drop_gp(g, m)
-    assert s.gp_size(g) == size
-    after = snap()
-    assert len(before) == len(after) and all(np.array_equal(a, b) for a, b in zip(before, after))
 
 
 def test_refusals_leave_the_gp_unchanged():
@@ -320,62 +224,17 @@ def test_tightening_and_solve_after_drop():
     identical statuses; x, u and variance() agree within 1e-6 (1 + |.|), the append's closed-loop
     bound.  A step of handle A that follows a drop computes its first linearisation afresh (stats
     slot 9 advances by sqp_iter + 1, against sqp_iter for a cache hit)."""
-    torch = _torch()
-    from gpmpc.solver import BatchSolver
-
-    H, B, tol = 5, 8, 1e-9
-    spec, data, hyp = problem("quad2d", 64)
-    mats = lqr(spec)
-    traj = spec.reference_trajectory()
-    x0, phase = initial_states(spec, traj, B)
-
-    def handle(lo, hi):
-        s = BatchSolver(spec, H, B, tol=tol, qp_tol=1e-11, qp_max_iter=100)
-        s.set_gps(product_gps([(X[lo:hi], y[lo:hi]) for X, y in data], hyp))
-        s.set_tightening(True, 0.95, *mats)
-        s.reset(reset_iterate=True)
-        return s
-
-    sa, sb = handle(0, 64), handle(16, 64)
-    stats = torch.zeros(B, sa.STATS_SLOTS, dtype=torch.int64, device="cuda")
-    sa.set_stats(stats)
+    loop = U.ClosedLoop(64)
+    sa, sb = (loop.handle([(X[lo:], y[lo:]) for X, y in loop.data], loop.hyp) for lo in (0, 16))
+    loop.start(sa, sb)
     for g in range(2):
         sa.reserve_gp(g, 64)
         assert sa.drop_gp(g, 16).cpu().tolist() == [1]
     assert [sa.gp_size(g) for g in range(2)] == [(48, 64)] * 2
-    obs = [torch.tensor(x0, device="cuda"), torch.tensor(x0, device="cuda")]
-    ts = [torch.tensor(phase, dtype=torch.int32, device="cuda") for _ in range(2)]
-    lin_prev = stats[:, 9].clone()
-
-    def step(i, s):
-        u = s.solve(obs[i], ts[i].clone())
-        out = dict(st=s.status.cpu().numpy(), it=s.sqp_iter.cpu().numpy())
-        out["x"], out["u"], _ = (t.cpu().numpy() for t in s.solution())
-        obs[i] = s.plant_step(obs[i], u.clone(), ts[i])
-        return out
-
-    def close(a, b):
-        return float((np.abs(a - b) / (1 + np.abs(b))).max())
-
-    for k in range(3):
-        ra, rb = step(0, sa), step(1, sb)
-        np.testing.assert_array_equal(ra["st"], rb["st"])
-        assert np.isin(ra["st"], (0, 2)).all(), ra["st"]
-        assert close(ra["x"], rb["x"]) <= 1e-6 and close(ra["u"], rb["u"]) <= 1e-6, (k, close(ra["x"], rb["x"]))
-        if k > 0:   # (the first step after a reset runs no variance launch)
-            va, vb = sa.variance().cpu().numpy(), sb.variance().cpu().numpy()
-            assert close(va, vb) <= 1e-6, (k, close(va, vb))
-        lin = stats[:, 9].clone()
-        d = (lin - lin_prev).cpu().numpy()
-        # step 0 follows the drop (and the reset): no cached rows; steps 1, 2 read the cache
-        np.testing.assert_array_equal(d, ra["it"] + (1 if k == 0 else 0))
-        lin_prev = lin
+    loop.three_steps()
     for g in range(2):
         assert sa.drop_gp(g, 8).cpu().tolist() == [1]
-    ra = step(0, sa)
-    d = (stats[:, 9] - lin_prev).cpu().numpy()
-    assert (d > 0).all()
-    np.testing.assert_array_equal(d, ra["it"] + 1)   # the cache served nothing computed with the old model
+    loop.step_after_update()
 
 
 def test_zz_report_ratios():

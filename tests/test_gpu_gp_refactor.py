@@ -25,82 +25,25 @@ import pytest
 import gp_drop_ref as D
 import gp_ref as R
 import gp_refactor_ref as G
+import gp_update_util as U
 from gp_append_ref import MARGIN, reference, worst_ratio
-from helpers import initial_states, lqr, problem, product_gps
+from gp_update_util import GUARD, QUANT, REFKEY, SF2, SN2
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not R.have_extended(), reason="np.longdouble is not wider than float64")]
 
-SF2, SN2 = G.SF2, G.SN2
-GUARD = 64
-SENTINEL = -7.25e77
 RATIOS: dict = {}
+_torch = U.gpu_torch
+_gp_objects = U.gp_objects
+_guarded = U.guarded
+_hyp = U.hyp
+_nan_block = U.nan_block
+_outputs = U.outputs
+_upload = U.upload
 
 
-def _torch():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-_SOLVERS: dict = {}
-
-
-def _solver(key, H=5, B=2, **kw):
-    _torch()
-    from gpmpc.models import get_spec
-    from gpmpc.solver import BatchSolver
-
-    if key not in _SOLVERS:
-        _SOLVERS[key] = BatchSolver(get_spec("quad2d"), H, B, **kw)
-    return _SOLVERS[key]
-
-
-def _hyp(dg):
-    return dg["ell"], SF2, SN2
-
-
-def _gp_objects(data, rows, hyps=None):
-    torch = _torch()
-    from gpmpc.gp import GaussianProcess
-
-    gps = []
-    for g, dg in enumerate(data):
-        gp = GaussianProcess(torch.tensor(dg["X"][rows]), torch.tensor(dg["y"][rows]))
-        gp.set_hyperparameters(*(_hyp(dg) if hyps is None else hyps[g]))
-        gps.append(gp)
-    return gps
-
-
-def _upload(s, data, rows, capacity=None, hyps=None):
-    s.set_gps(_gp_objects(data, rows, hyps))
-    if capacity is not None:
-        for g in range(2):
-            s.reserve_gp(g, capacity)
-
-
-def _guarded(P, dtype=None):
-    torch = _torch()
-    if dtype is torch.int32:
-        t = torch.full((P + GUARD,), -77, dtype=torch.int32, device="cuda")
-        t[P:] = -99
-        return t
-    t = torch.full((P + GUARD,), float("nan"), dtype=torch.float64, device="cuda")
-    t[P:] = SENTINEL
-    return t
-
-
-def _read(t, P, what):
-    a = t.cpu().numpy()
-    if a.dtype == np.int32:
-        assert (a[P:] == -99).all(), f"{what}: wrote past the end of the output"
-        assert (a[:P] != -77).all(), f"{what}: output not written"
-        return a[:P].copy()
-    assert (a[P:] == SENTINEL).all(), f"{what}: wrote past the end of the output"
-    assert not np.isnan(a[:P]).any(), f"{what}: {int(np.isnan(a[:P]).sum())} of {P} outputs not written"
-    return a[:P].copy()
+def _solver(key):
+    return U.solver(__name__, key)
 
 
 def _refactor(s, g, y, hyp, what):
@@ -112,32 +55,13 @@ def _refactor(s, g, y, hyp, what):
     fl = _guarded(1, torch.int32)
     _lib.check(s.lib.gpmpc_gp_refactor(s._h, g, yt.data_ptr(), *[float(v) for v in hyp], fl.data_ptr(), s._stream()))
     torch.cuda.synchronize()
-    return int(_read(fl, 1, what + " flag")[0])
+    return int(U.read(fl, 1, what + " flag")[0])
 
 
 def _scramble(s, g, y, hyp):
     """Leave GP g with another factor, other weights and another tile pack than the ones wanted."""
     ell, sf2, sn2 = hyp
     assert s.refactor_gp(g, 2.0 - np.asarray(y), 1.3 * ell, 3.0 * sf2, 10.0 * sn2).cpu().tolist() == [1]
-
-
-def _outputs(s, g, Z, what):
-    """gp_predict mean / predictive variance and gp_mean_grad mean / gradient at Z, guarded."""
-    torch = _torch()
-    from gpmpc import _lib
-
-    P, d = Z.shape
-    Zt = torch.tensor(np.ascontiguousarray(Z), device="cuda")
-    mb, vb, gm, gg = _guarded(P), _guarded(P), _guarded(P), _guarded(P * d)
-    s.gp_predict(g, Zt, with_noise=True, mean=mb, var=vb)
-    _lib.check(s.lib.gpmpc_gp_mean_grad(s._h, g, Zt.data_ptr(), P, gm.data_ptr(), gg.data_ptr(), s._stream()))
-    torch.cuda.synchronize()
-    return dict(mean=_read(mb, P, what + " mean"), var=_read(vb, P, what + " var"),
-                tmean=_read(gm, P, what + " tile mean"), grad=_read(gg, P * d, what + " grad").reshape(P, d))
-
-
-REFKEY = dict(mean="mean", var="var", tmean="mean", grad="grad")
-QUANT = ("mean", "var", "tmean", "grad")
 
 
 def _compare(case, g, got, full, ref, bound=None, record=True):
@@ -211,13 +135,6 @@ def test_restores_the_yardstick_after_drift():
         assert _refactor(sa, g, dg["y"][last], _hyp(dg), "after drift") == 1
         assert sa.gp_size(g) == (64, 64)
         _compare("after drift", g, _outputs(sa, g, dg["Z"], f"refreshed gp{g}"), full, refs[g])
-
-
-def _nan_block(s, g, d, m, seed):
-    rng = np.random.default_rng(seed)
-    Xb, yb = rng.uniform(-1, 1, (m, d)), rng.uniform(0.5, 1.5, m)
-    yb[m // 2] = np.nan
-    assert s.append_gp(g, Xb, yb).cpu().tolist() == [0]
 
 
 def test_inert_rows_stay_inert():
@@ -321,26 +238,14 @@ def _refused(s, g, dg, code, cause, y="targets", hyp=None, var=True):
     torch = _torch()
     from gpmpc import _lib
 
-    Zt = torch.tensor(dg["Z"], device="cuda")
-
-    def snap():
-        mu, v = s.gp_predict(g, Zt, with_noise=True, var=var)
-        tm, tg = s.gp_mean_grad(g, Zt)
-        torch.cuda.synchronize()
-        return [t.cpu().numpy() for t in (mu, v, tm, tg) if t is not None]
-
-    before, size = snap(), s.gp_size(g)
-    yt = None if y is None else torch.tensor(dg["y"][:size[0]], device="cuda")
     fl = _guarded(1, torch.int32)
     hyp = _hyp(dg) if hyp is None else hyp
-    with pytest.raises(_lib.GPMPCError, match=rf"error {code}: .*{cause}"):
+    with U.refused(s, g, dg, code, cause, var) as size:
+        yt = None if y is None else torch.tensor(dg["y"][:size[0]], device="cuda")
         _lib.check(s.lib.gpmpc_gp_refactor(s._h, g, None if yt is None else yt.data_ptr(), *[float(v) for v in hyp],
                                            fl.data_ptr(), s._stream()))
     torch.cuda.synchronize()
     assert (fl.cpu().numpy() == np.r_[-77, [-99] * GUARD]).all()   # nothing was queued
-    assert s.gp_size(g) == size
-    after = snap()
-    assert len(before) == len(after) and all(np.array_equal(a, b) for a, b in zip(before, after))
 
 
 def test_refusals_leave_the_gp_unchanged():
@@ -395,63 +300,19 @@ def test_closed_loop_after_new_hyperparameters():
     variance() agree within 1e-6 (1 + |.|), the append's and the drop's closed-loop bound.  A step of
     handle A that follows a refactorisation computes its first linearisation afresh (stats slot 9
     advances by sqp_iter + 1, against sqp_iter for a cache hit)."""
-    torch = _torch()
-    from gpmpc.solver import BatchSolver
-
-    H, B, tol = 5, 8, 1e-9
-    spec, data, hyp = problem("quad2d", 64)
+    loop = U.ClosedLoop(64)
+    data, hyp = loop.data, loop.hyp
     new = [(0.8 * h[0], 2.0 * h[1], 5.0 * h[2]) for h in hyp]
-    mats = lqr(spec)
-    traj = spec.reference_trajectory()
-    x0, phase = initial_states(spec, traj, B)
-
-    def handle(hy):
-        s = BatchSolver(spec, H, B, tol=tol, qp_tol=1e-11, qp_max_iter=100)
-        s.set_gps(product_gps(data, hy))
-        s.set_tightening(True, 0.95, *mats)
-        s.reset(reset_iterate=True)
-        return s
-
-    sa, sb = handle(hyp), handle(new)
-    stats = torch.zeros(B, sa.STATS_SLOTS, dtype=torch.int64, device="cuda")
-    sa.set_stats(stats)
+    sa, sb = loop.handle(data, hyp), loop.handle(data, new)
+    loop.start(sa, sb)
     for g in range(2):
         sa.reserve_gp(g, 64)
         assert sa.refactor_gp(g, data[g][1], *new[g]).cpu().tolist() == [1]
     assert [sa.gp_size(g) for g in range(2)] == [(64, 64)] * 2
-    obs = [torch.tensor(x0, device="cuda"), torch.tensor(x0, device="cuda")]
-    ts = [torch.tensor(phase, dtype=torch.int32, device="cuda") for _ in range(2)]
-    lin_prev = stats[:, 9].clone()
-
-    def step(i, s):
-        u = s.solve(obs[i], ts[i].clone())
-        out = dict(st=s.status.cpu().numpy(), it=s.sqp_iter.cpu().numpy())
-        out["x"], out["u"], _ = (t.cpu().numpy() for t in s.solution())
-        obs[i] = s.plant_step(obs[i], u.clone(), ts[i])
-        return out
-
-    def close(a, b):
-        return float((np.abs(a - b) / (1 + np.abs(b))).max())
-
-    for k in range(3):
-        ra, rb = step(0, sa), step(1, sb)
-        np.testing.assert_array_equal(ra["st"], rb["st"])
-        assert np.isin(ra["st"], (0, 2)).all(), ra["st"]
-        assert close(ra["x"], rb["x"]) <= 1e-6 and close(ra["u"], rb["u"]) <= 1e-6, (k, close(ra["x"], rb["x"]))
-        if k > 0:   # (the first step after a reset runs no variance launch)
-            va, vb = sa.variance().cpu().numpy(), sb.variance().cpu().numpy()
-            assert close(va, vb) <= 1e-6, (k, close(va, vb))
-        lin = stats[:, 9].clone()
-        d = (lin - lin_prev).cpu().numpy()
-        # step 0 follows the refactorisation (and the reset): no cached rows; steps 1, 2 read the cache
-        np.testing.assert_array_equal(d, ra["it"] + (1 if k == 0 else 0))
-        lin_prev = lin
+    loop.three_steps()
     for g in range(2):
         assert sa.refactor_gp(g, data[g][1], *hyp[g]).cpu().tolist() == [1]
-    ra = step(0, sa)
-    d = (stats[:, 9] - lin_prev).cpu().numpy()
-    assert (d > 0).all()
-    np.testing.assert_array_equal(d, ra["it"] + 1)   # the cache served nothing computed with the old model
+    loop.step_after_update()
 
 
 def test_zz_report_ratios():
