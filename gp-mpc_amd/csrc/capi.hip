@@ -65,13 +65,14 @@ struct GPSlot {
     double *rows = nullptr, *vrows = nullptr, *linvT = nullptr, *tiles = nullptr;   // tiles: tX | tW (MFMA tile pack)
     double* linvT_alt = nullptr;   // second factor buffer: the factor moves to it when npad changes, the two swap roles
     double *app = nullptr, *drp = nullptr, *rfc = nullptr;   // scratch of gpmpc_gp_append / _drop_oldest / _refactor
+    double* fit = nullptr;         // tile partials and state block of gpmpc_gp_mll / _fit
     double* vroot = nullptr;       // LOVE root (tightening only), its padded columns and its rank
     int vroot_cols = 0, vroot_rank = 0;
     // The slot's device buffers: the kReserved ones gpmpc_gp_reserve replaces, then the others
-    static constexpr int kReserved = 7, kBuffers = 9;
+    static constexpr int kReserved = 8, kBuffers = 10;
     static constexpr double* GPSlot::*kBuffer[kBuffers] = {&GPSlot::rows,  &GPSlot::tiles, &GPSlot::linvT,
                                                             &GPSlot::linvT_alt, &GPSlot::app, &GPSlot::drp,
-                                                            &GPSlot::rfc, &GPSlot::vrows, &GPSlot::vroot};
+                                                            &GPSlot::rfc, &GPSlot::fit, &GPSlot::vrows, &GPSlot::vroot};
     hipError_t release(int count) {   // frees and clears the first `count` of them; returns the first error
         hipError_t first = hipSuccess;
         for (int i = 0; i < count; ++i) {
@@ -101,6 +102,10 @@ struct DropLayout {
 // L_kk^-1 [c/16][256] | w [c] | masked targets [c] | the inert mask [c] int32 (in c/2 doubles) | status word
 struct RefactorLayout {
     size_t c, dinv = 0, w = 16 * c, ym = w + c, mask = ym + c, flag = mask + c / 2, end = flag + 1;
+};
+// the lower tiles' partial sums [c/16 (c/16 + 1) / 2][3] | the fit-state block (gpmpc_common.h kFit*)
+struct FitLayout {
+    size_t c, part = 0, state = 3 * ((c / 16) * (c / 16 + 1) / 2), end = state + kFitDoubles;
 };
 constexpr bool layouts_hold(size_t c) {
     return AppendLayout{c}.end == 16 * c + c + 256 + 16 + 1 && AppendLayout{c}.flag == 17 * c + 272 &&
@@ -547,6 +552,8 @@ struct GPUpdate {
 static const GPUpdate kAppend{"append", "takes appended rows", "the old training set", nullptr};
 static const GPUpdate kDrop{"drop", "drops rows", "the old training set", &GPSlot::drp};
 static const GPUpdate kRefactor{"refactor", "is refactorised", "the old factor", &GPSlot::rfc};
+static const GPUpdate kMll{"the likelihood", "has its likelihood evaluated", "the old factor", &GPSlot::fit};
+static const GPUpdate kFit{"fit", "is fitted", "the old factor", &GPSlot::fit};
 
 // What the three updates ask first, in this order (bad_args: what is wrong with the call's own arguments, or
 // null).  gpmpc_gp_reserve asks the same up to the exact upload (factor = false).
@@ -590,6 +597,7 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
         {&fresh.app, lin ? AppendLayout{cpad}.end : 0, true},
         {&fresh.drp, lin ? DropLayout{cpad}.end : 0, true},
         {&fresh.rfc, lin ? RefactorLayout{cpad}.end : 0, true},
+        {&fresh.fit, lin ? FitLayout{cpad}.end : 0, true},
     };
     hipError_t e = hipSuccess;
     auto undo = [&](gpmpc_status st, const char* what) {
@@ -756,24 +764,13 @@ gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int
     return GPMPC_OK;
 }
 
-gpmpc_status gpmpc_gp_refactor(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double lengthscale,
-                               double outputscale, double noise, int32_t* ok_dev, void* stream) {
-    const bool hyp_ok = std::isfinite(lengthscale) && lengthscale > 0.0 && std::isfinite(outputscale) &&
-                        outputscale > 0.0 && std::isfinite(noise) && noise > 0.0;
-    const gpmpc_status ready =
-        gp_update_ready(h, gp_id, kRefactor,
-                        !y_dev ? "no targets" : !hyp_ok ? "hyperparameters must be finite and positive" : nullptr);
-    if (ready != GPMPC_OK) return ready;
-    GPSlot& gs = h->gp[gp_id];
-    GPDev& g = h->P.gp[gp_id];
-    (void)hipSetDevice(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(order_after_last(h, s));
-    StreamMark mark{h, s};
+// The refactorisation of GP gp_id as launch_gp_refactor and the fit's iterations take it
+static GPRefactor refactor_args(gpmpc_handle* h, int gp_id, const double* y_dev, double inv_ell2, double sf2, double sn2,
+                                int32_t* ok_dev) {
+    const GPSlot& gs = h->gp[gp_id];
+    const GPDev& g = h->P.gp[gp_id];
     const int cpad = (gs.cap + 15) / 16 * 16;
     const RefactorLayout lay{(size_t)cpad};
-    // the model changes with the first launch queued: the cache must not serve its old rows
-    bump_lin(h);
     GPRefactor a{};
     a.rows = gs.rows;
     a.tX = gs.tiles;
@@ -785,20 +782,129 @@ gpmpc_status gpmpc_gp_refactor(gpmpc_handle* h, int32_t gp_id, const double* y_d
     a.n = g.n;
     a.d = h->md.gp_dim[gp_id];
     for (int k = 0; k < 3; ++k) a.xbar[k] = g.xbar[k];
-    a.inv_ell2 = 1.0 / (lengthscale * lengthscale);
-    a.sf2 = outputscale;
-    a.sn2 = noise;
+    a.inv_ell2 = inv_ell2;
+    a.sf2 = sf2;
+    a.sn2 = sn2;
     a.dinv = gs.rfc + lay.dinv;
     a.w = gs.rfc + lay.w;
     a.ym = gs.rfc + lay.ym;
     a.mask = reinterpret_cast<int32_t*>(gs.rfc + lay.mask);
     a.flag = reinterpret_cast<int32_t*>(gs.rfc + lay.flag);
     a.ok = ok_dev;
+    return a;
+}
+
+// What gpmpc_gp_mll and the fit's iterations read of GP gp_id, and the fit scratch
+static GPFit fit_args(gpmpc_handle* h, int gp_id, const double* y_dev) {
+    const GPSlot& gs = h->gp[gp_id];
+    const FitLayout lay{(size_t)((gs.cap + 15) / 16 * 16)};
+    GPFit f{};
+    f.rows = gs.rows;
+    f.linvT = gs.linvT;
+    f.y = y_dev;
+    f.npad = gs.npad;
+    f.n = h->P.gp[gp_id].n;
+    f.part = gs.fit + lay.part;
+    f.state = gs.fit + lay.state;
+    return f;
+}
+
+gpmpc_status gpmpc_gp_refactor(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double lengthscale,
+                               double outputscale, double noise, int32_t* ok_dev, void* stream) {
+    const bool hyp_ok = std::isfinite(lengthscale) && lengthscale > 0.0 && std::isfinite(outputscale) &&
+                        outputscale > 0.0 && std::isfinite(noise) && noise > 0.0;
+    const gpmpc_status ready =
+        gp_update_ready(h, gp_id, kRefactor,
+                        !y_dev ? "no targets" : !hyp_ok ? "hyperparameters must be finite and positive" : nullptr);
+    if (ready != GPMPC_OK) return ready;
+    GPDev& g = h->P.gp[gp_id];
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    // the model changes with the first launch queued: the cache must not serve its old rows
+    bump_lin(h);
+    const GPRefactor a = refactor_args(h, gp_id, y_dev, 1.0 / (lengthscale * lengthscale), outputscale, noise, ok_dev);
     HIPCHK(launch_gp_refactor(a, s));
     // every kernel reads the hyperparameters from the handle: they change with the factor
     g.inv_ell2 = a.inv_ell2;
     g.sf2 = a.sf2;
     g.sn2 = a.sn2;
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_mll(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double* out_dev, void* stream) {
+    const gpmpc_status ready = gp_update_ready(h, gp_id, kMll, (!y_dev || !out_dev) ? "no targets or no output" : nullptr);
+    if (ready != GPMPC_OK) return ready;
+    const GPDev& g = h->P.gp[gp_id];
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const GPFit f = fit_args(h, gp_id, y_dev);
+    HIPCHK(launch_gp_fit_set_hyp(f.state, g.inv_ell2, g.sf2, g.sn2, s));
+    HIPCHK(launch_gp_fit_eval(f, out_dev, s));
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_fit(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double lr, int32_t max_iter, double* raw,
+                          int32_t* iters_out, int32_t* ok_out, double* hist_dev, void* stream) {
+    const char* bad = nullptr;
+    if (!y_dev) bad = "no targets";
+    else if (!raw) bad = "no raw parameters";
+    else if (!std::isfinite(raw[0]) || !std::isfinite(raw[1]) || !std::isfinite(raw[2])) bad = "raw parameters must be finite";
+    else if (!std::isfinite(lr) || !(lr > 0.0)) bad = "the learning rate must be finite and positive";
+    else if (max_iter < 1) bad = "at least one iteration";
+    const gpmpc_status ready = gp_update_ready(h, gp_id, kFit, bad);
+    if (ready != GPMPC_OK) return ready;
+    GPDev& g = h->P.gp[gp_id];
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    // the model changes with the first launch queued: the cache must not serve its old rows
+    bump_lin(h);
+    // the iterations' factorisations: the hyperparameters come from the state block, the tile pack they write is
+    // rewritten at the end, no status word but the scratch's own
+    const GPRefactor a = refactor_args(h, gp_id, y_dev, g.inv_ell2, g.sf2, g.sn2, nullptr);
+    const GPFit f = fit_args(h, gp_id, y_dev);
+    HIPCHK(launch_gp_refactor_begin(a, s));
+    HIPCHK(launch_gp_fit_init(f.state, raw, s));
+    // the stop and fail flags are read back once per kFitQueue iterations; what is queued past a stop changes nothing
+    constexpr int kFitQueue = 8;
+    double st[kFitDoubles];
+    for (int done = 0; done < max_iter;) {
+        const int q = std::min(kFitQueue, max_iter - done);
+        for (int i = 0; i < q; ++i) HIPCHK(launch_gp_fit_iteration(a, f, lr, hist_dev, s));
+        done += q;
+        HIPCHK(hipMemcpyAsync(st, f.state, sizeof(st), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (st[kFitStop] != 0.0 || st[kFitFail] != 0.0) break;
+    }
+    const bool fitted = st[kFitFail] == 0.0;
+    // softplus as the device computes it (torch's, threshold 20)
+    auto sp = [](double x) { return x > 20.0 ? x : std::log1p(std::exp(x)); };
+    double inv_ell2 = g.inv_ell2, sf2 = g.sf2, sn2 = g.sn2;
+    if (fitted) {
+        const double ell = sp(st[kFitRaw]);
+        inv_ell2 = 1.0 / (ell * ell);
+        sf2 = sp(st[kFitRaw + 1]);
+        sn2 = 1e-6 + sp(st[kFitRaw + 2]);
+    }
+    // the ordinary refactorisation at the fitted hyperparameters (after a failure: at the ones the GP had)
+    GPRefactor last = a;
+    last.inv_ell2 = inv_ell2, last.sf2 = sf2, last.sn2 = sn2;
+    HIPCHK(launch_gp_refactor(last, s));
+    g.inv_ell2 = inv_ell2;
+    g.sf2 = sf2;
+    g.sn2 = sn2;
+    int32_t flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, last.flag, sizeof(flag), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (fitted)
+        for (int k = 0; k < 3; ++k) raw[k] = st[kFitRaw + k];
+    if (iters_out) *iters_out = (int32_t)st[kFitStep];
+    if (ok_out) *ok_out = (fitted && flag == 1) ? 1 : 0;
     return GPMPC_OK;
 }
 

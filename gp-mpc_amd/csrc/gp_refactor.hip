@@ -29,7 +29,9 @@
 // gp_refactor_alpha_kernel alpha (one wave per row: every lane sums its columns in ascending order,
 // then a fixed butterfly), rows[.][3], tX, tW and the status.  2 nt + 4 plain launches and one
 // 4-byte memset on the caller's stream; no sum crosses waves except through memory in a fixed order,
-// no floating-point atomics, no grid-wide barrier.
+// no floating-point atomics, no grid-wide barrier.  launch_gp_refactor is three pieces (begin, factor,
+// solve) around the build; the hyperparameter fit (gp_fit.hip) queues the same pieces around a build of
+// its own.
 //
 // Inert rows (rejected append blocks) and the padding rows past n have a zero on the old factor's
 // diagonal.  They take part as identity rows of Khat (diagonal 1, off-diagonal 0), so their row and
@@ -257,22 +259,42 @@ __global__ __launch_bounds__(64 * kRefWaves) void gp_refactor_alpha_kernel(GPRef
     tile_write_w(a.tW, slot, al, xc);
 }
 
-hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream) {
-    if (a.n < 1 || a.npad % 16 != 0 || a.n > a.npad) return hipErrorInvalidValue;
-    const int nt = a.npad / 16, nb = (a.npad + 255) / 256, tb = (nt + kRefWaves - 1) / kRefWaves;
+static bool refactor_shape_ok(const GPRefactor& a) { return a.n >= 1 && a.npad % 16 == 0 && a.n <= a.npad; }
+
+hipError_t launch_gp_refactor_begin(const GPRefactor& a, hipStream_t stream) {
+    if (!refactor_shape_ok(a)) return hipErrorInvalidValue;
     hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.flag), 1, 1, stream);   // the status starts at 1
     if (e != hipSuccess) return e;
-    GP_LAUNCH(gp_refactor_mask_kernel, dim3(nb), dim3(256), stream, a);
-    GP_LAUNCH(gp_refactor_build_kernel, dim3(nt, nt), dim3(256), stream, a);
+    GP_LAUNCH(gp_refactor_mask_kernel, dim3((a.npad + 255) / 256), dim3(256), stream, a);
+    return hipSuccess;
+}
+
+hipError_t launch_gp_refactor_factor(const GPRefactor& a, hipStream_t stream) {
+    if (!refactor_shape_ok(a)) return hipErrorInvalidValue;
+    const int nt = a.npad / 16, tb = (nt + kRefWaves - 1) / kRefWaves;
     for (int k = 0; k < nt; ++k) {
         const int below = nt - k - 1;
         GP_LAUNCH(gp_refactor_panel_kernel, dim3(std::max(1, (below + kRefWaves - 1) / kRefWaves)), dim3(64 * kRefWaves),
                   stream, a, k);
         GP_LAUNCH(gp_refactor_update_kernel, dim3(tb, nt - k), dim3(64 * kRefWaves), stream, a, k);
     }
+    return hipSuccess;
+}
+
+hipError_t launch_gp_refactor_solve(const GPRefactor& a, hipStream_t stream) {
+    if (!refactor_shape_ok(a)) return hipErrorInvalidValue;
     GP_LAUNCH(gp_refactor_w_kernel, dim3((a.npad + 63) / 64), dim3(1024), stream, a);
     GP_LAUNCH(gp_refactor_alpha_kernel, dim3((a.npad + kRefWaves - 1) / kRefWaves), dim3(64 * kRefWaves), stream, a);
     return hipSuccess;
+}
+
+hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream) {
+    hipError_t e = launch_gp_refactor_begin(a, stream);
+    if (e != hipSuccess) return e;
+    const int nt = a.npad / 16;
+    GP_LAUNCH(gp_refactor_build_kernel, dim3(nt, nt), dim3(256), stream, a);
+    e = launch_gp_refactor_factor(a, stream);
+    return e != hipSuccess ? e : launch_gp_refactor_solve(a, stream);
 }
 
 }  // namespace gpmpc

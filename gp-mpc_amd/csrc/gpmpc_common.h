@@ -352,11 +352,42 @@ struct GPRefactor {
     int32_t* ok;          // the caller's status word, may be null
 };
 
-// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip, gp_refactor.hip; what the last three
-// share, the tile pack's layout included, is in gp_tile.h).
+// The marginal log likelihood of an exact GP and its gradient from the factor the handle holds, and the
+// hyperparameter fit built on it (gp_fit.hip; gpmpc_gp_mll and gpmpc_gp_fit fill it).  Nothing of the GP
+// is written through it.
+struct GPFit {
+    const double* rows;   // [>= npad][4], GPDev::rows: inputs and alpha = rows[.][3]
+    const double* linvT;  // [npad][npad], the live factor (a zero on its diagonal: an inert or padding row)
+    const double* y;      // [n] targets in row order (device); inert rows' entries are not read into sums
+    int32_t npad;
+    int32_t n;
+    double* part;         // [nt (nt + 1) / 2][3], nt = npad / 16: the tiles' partial sums, tile (I, J) at I (I + 1) / 2 + J
+    double* state;        // the fit-state block (kFit* below)
+};
+// The fit-state block, in doubles: raw parameters, Adam's moments, its step count (= iterations done),
+// the last loss, the stop and fail flags, the constrained hyperparameters the next factorisation reads
+// {1 / ell^2, sf2, sn2, ell} and the last evaluation {MLL / n_live, d/d ell, d/d sf2, d/d sn2}
+enum : int { kFitRaw = 0, kFitM = 3, kFitV = 6, kFitStep = 9, kFitLast = 10, kFitStop = 11, kFitFail = 12,
+             kFitHyp = 16, kFitOut = 20, kFitDoubles = 24 };
+
+// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip, gp_refactor.hip, gp_fit.hip; what the
+// last four share, the tile pack's layout included, is in gp_tile.h).
 hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream);
 hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream);
 hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream);
+// Its pieces, which the fit's iterations queue around a Khat built from device-resident hyperparameters:
+// the status word set to 1 and the inert mask / masked targets; the 2 nt panel and update launches on a
+// Khat already in A (linvT zeroed); w, alpha, rows[.][3], tX / tW and the caller's status word
+hipError_t launch_gp_refactor_begin(const GPRefactor& a, hipStream_t stream);
+hipError_t launch_gp_refactor_factor(const GPRefactor& a, hipStream_t stream);
+hipError_t launch_gp_refactor_solve(const GPRefactor& a, hipStream_t stream);
+// {1 / ell^2, sf2, sn2, ell} into state[kFitHyp ..]; then {MLL / n_live and its gradient} into out[4]
+hipError_t launch_gp_fit_set_hyp(double* state, double inv_ell2, double sf2, double sn2, hipStream_t stream);
+hipError_t launch_gp_fit_eval(const GPFit& f, double* out, hipStream_t stream);
+// The fit: the state block from the raw start; one iteration (factorise at state's hyperparameters through
+// `a`, evaluate, Adam step with the early-stop rule; hist: [max_iter][4] or null, row = the step taken)
+hipError_t launch_gp_fit_init(double* state, const double* raw, hipStream_t stream);
+hipError_t launch_gp_fit_iteration(const GPRefactor& a, const GPFit& f, double lr, double* hist_dev, hipStream_t stream);
 // count < 0: the whole batch; else ranks first .. first + count - 1 of order[] (launch_sqp_order)
 hipError_t launch_sqp(const ProblemDev& P, const StateDev& S, const StepIO& io, int batch, hipStream_t stream,
                       int first = 0, int count = -1);

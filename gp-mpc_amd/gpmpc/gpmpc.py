@@ -267,18 +267,39 @@ class GPMPC:
                 gp.set_hyperparameters(*hyp)
         return flags
 
-    def refit_hyperparameters(self, lr: float, iterations: int) -> list[torch.Tensor]:
-        """Refit the hyperparameters of the uploaded GPs on their current data (``fit_gp``, or
-        ``fit_gp_allreduce`` under more than one rank, as ``train_gp`` chooses) and apply them on the
-        device (``refresh_gps``): no upload, and the controller needs no ``reset()``.  Returns
-        ``refresh_gps``' flags."""
+    def refit_hyperparameters(self, lr: float, iterations: int, fit: str = "torch") -> list[torch.Tensor]:
+        """Refit the hyperparameters of the uploaded GPs on their current data and apply them on the
+        device: no upload, and the controller needs no ``reset()``.
+
+        ``fit="torch"``: ``fit_gp`` (``fit_gp_allreduce`` under more than one rank, as ``train_gp``
+        chooses) on the Python GP's copy of the data, then ``refresh_gps``, whose flags are returned.
+        ``fit="device"``: ``BatchSolver.fit_gp`` per GP, from the Python GP's current raw parameters
+        on the handle's own factor, inputs and scratch; the fitted raw parameters are written into the
+        Python GP objects (a GP whose fit failed keeps its own) and one int32 device flag per GP is
+        returned, like ``refresh_gps``'.  Single rank only: the data-parallel fit stays the torch one."""
         if self.sparse:
             raise _lib.GPMPCError("refit_hyperparameters: not available in sparse (FITC) mode")
+        if fit not in ("torch", "device"):
+            raise ValueError("fit must be 'torch' or 'device'")
         assert self.gaussian_process is not None and not self._requires_recompile, \
             "GP model must be uploaded (call reset())"
         from . import distributed as D
 
         _, size = D.world()
+        if fit == "device":
+            if size > 1:
+                raise _lib.GPMPCError("refit_hyperparameters: fit='device' runs on one rank (the data-parallel fit is "
+                                      "fit='torch')")
+            flags = []
+            for i, gp in enumerate(self.gaussian_process):
+                raw0 = [float(p) for p in gp.parameters()]
+                raw, _, ok = self.solver.fit_gp(i, gp.train_targets, raw0, lr, iterations)
+                if ok:
+                    for p, r in zip(gp.parameters(), raw):
+                        p.fill_(float(r))
+                    gp.K, gp.K_inv, gp._dev = None, None, None
+                flags.append(torch.tensor([ok], dtype=torch.int32, device=self.device))
+            return flags
         for gp in self.gaussian_process:
             if size > 1:
                 D.fit_gp_allreduce(gp, n_train=iterations, lr=lr)

@@ -216,16 +216,64 @@ class BatchSolver:
         device int32 tensor [1] (1: every live target finite and every pivot finite and positive; 0:
         the GP's contents are unspecified, upload it again).  The Python GP objects are not touched
         (``GaussianProcess.set_hyperparameters``)."""
-        y = torch.as_tensor(y).to(self.device, torch.float64).reshape(-1).contiguous()
-        # (an unset GP is the library's refusal, like every other precondition)
-        n = self.gp_size(gp_id)[0] if y.numel() else 0
-        if y.numel() and y.shape[0] != n:
-            raise ValueError(f"GP {gp_id} has {n} training rows, got {y.shape[0]} targets")
+        y = self._targets(gp_id, y)
         flag = torch.empty(1, dtype=torch.int32, device=self.device)
         _lib.check(self.lib.gpmpc_gp_refactor(self._h, int(gp_id), y.data_ptr() if y.numel() else None,
                                               float(lengthscale), float(outputscale), float(noise), flag.data_ptr(),
                                               self._stream()))
         return flag
+
+    def _targets(self, gp_id: int, y) -> torch.Tensor:
+        """The n targets of GP ``gp_id``'s current rows on the device (an unset GP is the library's refusal,
+        like every other precondition)."""
+        y = torch.as_tensor(y).to(self.device, torch.float64).reshape(-1).contiguous()
+        n = self.gp_size(gp_id)[0] if y.numel() else 0
+        if y.numel() and y.shape[0] != n:
+            raise ValueError(f"GP {gp_id} has {n} training rows, got {y.shape[0]} targets")
+        return y
+
+    def gp_mll(self, gp_id: int, y) -> torch.Tensor:
+        """Marginal log likelihood per live row of the handle's GP ``gp_id`` and its gradient, a device
+        tensor [4] = (MLL / n, d/d lengthscale, d/d outputscale, d/d noise), on the current stream
+        (gpmpc_gp_mll): from the factor, inputs and weights the handle holds and the targets ``y`` (n,)
+        of its n current rows (inert rows' entries are ignored).  Nothing of the GP changes; no
+        synchronisation of its own.  Needs ``reserve_gp``."""
+        y = self._targets(gp_id, y)
+        out = torch.empty(4, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.gpmpc_gp_mll(self._h, int(gp_id), y.data_ptr() if y.numel() else None, out.data_ptr(),
+                                         self._stream()))
+        return out
+
+    def fit_gp(self, gp_id: int, y, raw, lr: float, iterations: int, history=False):
+        """Fit the hyperparameters of the handle's GP ``gp_id`` on the device (gpmpc_gp_fit): the loop
+        of ``gpmpc.gp.fit_gp`` (Adam on -MLL / n over the raw softplus parameters, early stop at
+        |dloss| < 1e-3) from ``raw`` (3,), on the targets ``y`` (n,) of the GP's n current rows, with
+        no host round trip per iteration.  The call synchronises the current stream and leaves the GP
+        refactorised at the fitted hyperparameters.  Returns ``(raw, iters, ok)``: the fitted raw
+        parameters (numpy (3,); the ones passed in when ok is 0), the iterations run and the status.
+        ``history=True`` appends the (iters, 4) array of (loss before the step, raw after it);
+        a contiguous float64 device tensor of at least ``4 * iterations`` elements is written in place
+        and returned whole.  Needs ``reserve_gp``.  The Python GP objects are not touched."""
+        y = self._targets(gp_id, y)
+        raw = np.array(raw, dtype=np.float64).reshape(-1).copy()
+        if raw.shape[0] != 3:
+            raise ValueError("raw must hold the three raw parameters (lengthscale, outputscale, noise)")
+        iterations = int(iterations)
+        hist = None
+        if isinstance(history, torch.Tensor):
+            if history.dtype != torch.float64 or history.device != self.device or not history.is_contiguous() \
+                    or history.numel() < 4 * iterations:
+                raise ValueError(f"history must be a contiguous float64 tensor of >= {4 * iterations} elements on {self.device}")
+            hist = history
+        elif history:
+            hist = torch.empty(max(iterations, 1), 4, dtype=torch.float64, device=self.device)
+        iters, ok = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(self.lib.gpmpc_gp_fit(self._h, int(gp_id), y.data_ptr() if y.numel() else None, float(lr), iterations,
+                                         raw.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(iters),
+                                         ctypes.byref(ok), _lib.ptr(hist), self._stream()))
+        if hist is None:
+            return raw, iters.value, ok.value
+        return raw, iters.value, ok.value, (hist if isinstance(history, torch.Tensor) else hist[:iters.value].cpu().numpy())
 
     def gp_size(self, gp_id: int) -> tuple[int, int]:
         """(training rows, capacity) of the handle's GP ``gp_id`` (gpmpc_gp_size)."""

@@ -166,6 +166,38 @@ gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int
 gpmpc_status gpmpc_gp_refactor(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double lengthscale,
                                double outputscale, double noise, int32_t* ok_dev, void* stream);
 
+/* The exact marginal log likelihood per live row of GP gp_id as the handle holds it, and its gradient
+ * with respect to (lengthscale, outputscale, noise), on `stream`: out_dev [4] (device, float64) =
+ * {MLL / n_live, d/d lengthscale, d/d outputscale, d/d noise} (the ExactMarginalLogLikelihood
+ * convention; inert rows are not counted).  y_dev [n]: the targets of the GP's n current rows in row
+ * order, as gpmpc_gp_refactor takes them.  Everything comes from the handle's state (csrc/gp_fit.hip):
+ * log det from the diagonal of (L^-1)^T, alpha from the rows, K^-1 = L^-T L^-1 tile by tile on f64 MFMA
+ * for tr((alpha alpha^T - K^-1) dK/dtheta).  After appends and drops it is the likelihood of the factor
+ * as it has drifted.  Asynchronous, nothing read back; nothing of the GP changes.
+ * Refused: y_dev or out_dev NULL (GPMPC_ERR_ARG); every state refusal of gpmpc_gp_refactor
+ * (GPMPC_ERR_STATE; gpmpc_gp_reserve also allocates this call's scratch). */
+gpmpc_status gpmpc_gp_mll(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double* out_dev, void* stream);
+
+/* Fit the hyperparameters of GP gp_id on the device: Adam (lr, torch.optim.Adam's defaults) on
+ * -MLL / n_live over the raw parameters (lengthscale = softplus(raw[0]), outputscale =
+ * softplus(raw[1]), noise = 1e-6 + softplus(raw[2])), at most max_iter iterations, ended early after
+ * the step at which |previous loss - loss| < 1e-3.  Iteration t factorises at the raw parameters
+ * of iteration t - 1 (gpmpc_gp_refactor's kernels), evaluates loss and gradient (gpmpc_gp_mll's) and
+ * steps; parameters, moments and flags stay on the device, and the host reads the flags once per 8
+ * queued iterations.  THE CALL SYNCHRONISES `stream`: it returns after the GP has been refactorised
+ * at the fitted hyperparameters, bit for bit as gpmpc_gp_refactor(y_dev, those hyperparameters) leaves
+ * it, and the handle's hyperparameters are the fitted ones.
+ * raw: host [3], in: the start, out: the fitted raw parameters.  iters_out, ok_out: host, may be NULL;
+ * the iterations run and 1 for success.  hist_dev: device [max_iter][4] or NULL; row t - 1 receives
+ * (loss before step t, raw after it), rows past the iterations run are not written.
+ * Failure (a target of a live row, a pivot, a loss or a gradient that is not finite): *ok_out = 0, raw
+ * is left as passed in, and the GP is refactorised at the hyperparameters it had; if that
+ * refactorisation fails too (the targets), its contents are unspecified as after gpmpc_gp_refactor's 0.
+ * Refused, with the GP unchanged: y_dev or raw NULL, a raw value or lr that is not finite, lr <= 0,
+ * max_iter < 1 (GPMPC_ERR_ARG); every state refusal of gpmpc_gp_refactor (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_gp_fit(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double lr, int32_t max_iter, double* raw,
+                          int32_t* iters_out, int32_t* ok_out, double* hist_dev, void* stream);
+
 /* Training rows of GP gp_id (inert rows included) and its capacity; either may be NULL. */
 gpmpc_status gpmpc_gp_size(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* capacity);
 
