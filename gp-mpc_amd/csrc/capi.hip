@@ -66,13 +66,15 @@ struct GPSlot {
     double* linvT_alt = nullptr;   // second factor buffer: the factor moves to it when npad changes, the two swap roles
     double *app = nullptr, *drp = nullptr, *rfc = nullptr;   // scratch of gpmpc_gp_append / _drop_oldest / _refactor
     double* fit = nullptr;         // tile partials and state block of gpmpc_gp_mll / _fit
+    double* love = nullptr;        // Lanczos vectors, partial sums and state of gpmpc_gp_love_root
     double* vroot = nullptr;       // LOVE root (tightening only), its padded columns and its rank
     int vroot_cols = 0, vroot_rank = 0;
     // The slot's device buffers: the kReserved ones gpmpc_gp_reserve replaces, then the others
-    static constexpr int kReserved = 8, kBuffers = 10;
+    static constexpr int kReserved = 9, kBuffers = 11;
     static constexpr double* GPSlot::*kBuffer[kBuffers] = {&GPSlot::rows,  &GPSlot::tiles, &GPSlot::linvT,
                                                             &GPSlot::linvT_alt, &GPSlot::app, &GPSlot::drp,
-                                                            &GPSlot::rfc, &GPSlot::fit, &GPSlot::vrows, &GPSlot::vroot};
+                                                            &GPSlot::rfc, &GPSlot::fit, &GPSlot::love, &GPSlot::vrows,
+                                                            &GPSlot::vroot};
     hipError_t release(int count) {   // frees and clears the first `count` of them; returns the first error
         hipError_t first = hipSuccess;
         for (int i = 0; i < count; ++i) {
@@ -107,10 +109,20 @@ struct RefactorLayout {
 struct FitLayout {
     size_t c, part = 0, state = 3 * ((c / 16) * (c / 16 + 1) / 2), end = state + kFitDoubles;
 };
+// Q^T [256][c] | v [c] | the inert mask [c] int32 (in c/2 doubles) | parts of alpha [c/16] | parts of Q^T v, two
+// buffers [ceil(c/64)][256] each | parts of |v|^2 [ceil(c/64)] and of the live count [ceil(c/256)] | alpha, beta, the
+// bidiagonal factor's diagonal and subdiagonal [256] each | the state words (gpmpc_common.h kLove*)
+struct LoveLayout {
+    size_t c, nb = (c + 255) / 256, nbo = (c + 63) / 64, qt = 0, v = kLoveMaxRank * c, mask = v + c, apart = mask + c / 2,
+              cpa = apart + c / 16, cpb = cpa + 256 * nbo, npart = cpb + 256 * nbo, ipart = npart + nbo, alpha = ipart + nb,
+              beta = alpha + kLoveMaxRank, cd = beta + kLoveMaxRank, lsub = cd + kLoveMaxRank, state = lsub + kLoveMaxRank,
+              end = state + kLoveInts / 2;
+};
 constexpr bool layouts_hold(size_t c) {
     return AppendLayout{c}.end == 16 * c + c + 256 + 16 + 1 && AppendLayout{c}.flag == 17 * c + 272 &&
            DropLayout{c}.end == 61 * c + 1 && DropLayout{c}.srows == 49 * c && RefactorLayout{c}.mask == 18 * c &&
-           RefactorLayout{c}.end == 18 * c + c / 2 + 1;
+           RefactorLayout{c}.end == 18 * c + c / 2 + 1 && LoveLayout{c}.v == 256 * c &&
+           LoveLayout{c}.end == 257 * c + c / 2 + c / 16 + 513 * ((c + 63) / 64) + (c + 255) / 256 + 4 * 256 + 4;
 }
 static_assert(layouts_hold(16) && layouts_hold(4096), "scratch layouts of the GP updates changed size or offsets");
 }  // namespace
@@ -554,6 +566,8 @@ static const GPUpdate kDrop{"drop", "drops rows", "the old training set", &GPSlo
 static const GPUpdate kRefactor{"refactor", "is refactorised", "the old factor", &GPSlot::rfc};
 static const GPUpdate kMll{"the likelihood", "has its likelihood evaluated", "the old factor", &GPSlot::fit};
 static const GPUpdate kFit{"fit", "is fitted", "the old factor", &GPSlot::fit};
+// (root_of null: an installed root is no obstacle, the call replaces it)
+static const GPUpdate kLove{"the LOVE root", "has its LOVE root built", nullptr, &GPSlot::love};
 
 // What the three updates ask first, in this order (bad_args: what is wrong with the call's own arguments, or
 // null).  gpmpc_gp_reserve asks the same up to the exact upload (factor = false).
@@ -567,7 +581,7 @@ static gpmpc_status gp_update_ready(gpmpc_handle* h, int gp_id, const GPUpdate& 
     if (!gs.exact) return fail(GPMPC_ERR_STATE, std::string("FITC upload (Xv != X): only an exact GP ") + op.takes);
     if (!factor) return GPMPC_OK;
     if (!gs.linvT) return fail(GPMPC_ERR_STATE, std::string(op.verb) + " needs Linv (the GP was set without it)");
-    if (gs.vroot)
+    if (gs.vroot && op.root_of)
         return fail(GPMPC_ERR_STATE, std::string("a LOVE root is installed: it belongs to ") + op.root_of +
                                          " (drop it first, gpmpc_set_gp_variance_root with R = NULL)");
     if (op.scratch && (!(gs.*op.scratch) || !gs.linvT_alt))
@@ -598,6 +612,7 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
         {&fresh.drp, lin ? DropLayout{cpad}.end : 0, true},
         {&fresh.rfc, lin ? RefactorLayout{cpad}.end : 0, true},
         {&fresh.fit, lin ? FitLayout{cpad}.end : 0, true},
+        {&fresh.love, lin ? LoveLayout{cpad}.end : 0, true},
     };
     hipError_t e = hipSuccess;
     auto undo = [&](gpmpc_status st, const char* what) {
@@ -946,6 +961,101 @@ gpmpc_status gpmpc_set_gp_variance_root(gpmpc_handle* h, int32_t gp_id, int32_t 
     gs.vroot = buf;
     gs.vroot_cols = rpad;
     gs.vroot_rank = r;
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_love_root(gpmpc_handle* h, int32_t gp_id, int32_t rank, const double* q0_dev, int32_t* rank_out,
+                                int32_t* ok_out, void* stream) {
+    const gpmpc_status ready =
+        gp_update_ready(h, gp_id, kLove,
+                        !q0_dev ? "no start vector" : (rank < 1 || rank > kLoveMaxRank) ? "root rank must be 1..256" : nullptr);
+    if (ready != GPMPC_OK) return ready;
+    GPSlot& gs = h->gp[gp_id];
+    const GPDev& g = h->P.gp[gp_id];
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const int cpad = (gs.cap + 15) / 16 * 16;
+    const LoveLayout lay{(size_t)cpad};
+    GPLove a{};
+    a.rows = gs.rows;
+    a.linvT = gs.linvT;
+    a.A = gs.linvT_alt;
+    a.q0 = q0_dev;
+    a.npad = gs.npad;
+    a.n = g.n;
+    a.ld = cpad;
+    a.rank = rank;
+    a.inv_ell2 = g.inv_ell2;
+    a.sf2 = g.sf2;
+    a.sn2 = g.sn2;
+    a.qt = gs.love + lay.qt;
+    a.v = gs.love + lay.v;
+    a.mask = reinterpret_cast<int32_t*>(gs.love + lay.mask);
+    a.apart = gs.love + lay.apart;
+    a.cpa = gs.love + lay.cpa;
+    a.cpb = gs.love + lay.cpb;
+    a.npart = gs.love + lay.npart;
+    a.ipart = gs.love + lay.ipart;
+    a.alpha = gs.love + lay.alpha;
+    a.beta = gs.love + lay.beta;
+    a.cd = gs.love + lay.cd;
+    a.lsub = gs.love + lay.lsub;
+    a.state = reinterpret_cast<int32_t*>(gs.love + lay.state);
+    HIPCHK(launch_gp_love_begin(a, s));
+    // the done word is read back once per kLoveQueue iterations; what is queued past the stop changes nothing
+    constexpr int kLoveQueue = 8;
+    const int iters = std::min(rank, g.n);
+    int32_t st[kLoveInts] = {0};
+    for (int done = 0; done < iters && !st[kLoveDone];) {
+        const int q = std::min(kLoveQueue, iters - done);
+        for (int i = 0; i < q; ++i) HIPCHK(launch_gp_love_iteration(a, done + i, s));
+        done += q;
+        HIPCHK(hipMemcpyAsync(st, a.state, sizeof(st), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    const int m = st[kLoveM];
+    const bool ok = st[kLoveDone] == 1 && st[kLoveOk] == 1 && m >= 1 && m <= rank;
+    if (rank_out) *rank_out = ok ? m : 0;
+    if (ok_out) *ok_out = ok ? 1 : 0;
+    if (!ok) return GPMPC_OK;   // (the handle's root, if any, stays)
+    // staged in a local buffer: the handle's root, columns and rank change together, on success only
+    const int rp = (m + 15) / 16 * 16;
+    double* buf = nullptr;
+    hipError_t e = hipMalloc(&buf, (size_t)gs.npad * rp * sizeof(double));
+    if (e == hipSuccess) e = launch_gp_love_root(a, m, buf, rp, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        if (buf) (void)hipFree(buf);
+        if (rank_out) *rank_out = 0;
+        if (ok_out) *ok_out = 0;
+        return fail(GPMPC_ERR_HIP, std::string("LOVE root: ") + hipGetErrorString(e));
+    }
+    gs.drop_root();
+    gs.vroot = buf;
+    gs.vroot_cols = rp;
+    gs.vroot_rank = m;
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_get_gp_variance_root(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* r, double* R_dev,
+                                        void* stream) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
+    const GPSlot& gs = h->gp[gp_id];
+    if (!gs.set || !gs.vroot) return fail(GPMPC_ERR_STATE, "no LOVE root installed");
+    const int rows = h->P.gp[gp_id].nv;
+    if (n) *n = rows;
+    if (r) *r = gs.vroot_rank;
+    if (!R_dev) return GPMPC_OK;
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const size_t wb = (size_t)gs.vroot_rank * sizeof(double);
+    HIPCHK(hipMemcpy2DAsync(R_dev, wb, gs.vroot, (size_t)gs.vroot_cols * sizeof(double), wb, rows,
+                            hipMemcpyDeviceToDevice, s));
     return GPMPC_OK;
 }
 

@@ -370,8 +370,44 @@ struct GPFit {
 enum : int { kFitRaw = 0, kFitM = 3, kFitV = 6, kFitStep = 9, kFitLast = 10, kFitStop = 11, kFitFail = 12,
              kFitHyp = 16, kFitOut = 20, kFitDoubles = 24 };
 
-// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip, gp_refactor.hip, gp_fit.hip; what the
-// last four share, the tile pack's layout included, is in gp_tile.h).
+// The LOVE variance root of an exact GP built on the device (gp_love.hip; gpmpc_gp_love_root fills it): Lanczos
+// with full reorthogonalisation on Khat, generated into A, and the bidiagonal root of its tridiagonal matrix.
+// Nothing of the GP is written through it.
+constexpr int kLoveMaxRank = 256;
+struct GPLove {
+    const double* rows;   // [>= npad][4], GPDev::rows: the inputs
+    const double* linvT;  // [npad][npad], the live factor (a zero on its diagonal: an inert or padding row)
+    double* A;            // [npad][npad] work space (the second factor buffer): Khat in full
+    const double* q0;     // [n] the start vector (device); inert rows' entries are not read into sums
+    int32_t npad;         // n rounded up to 16
+    int32_t n;
+    int32_t ld;           // the padded capacity: stride of Qt's columns
+    int32_t rank;         // the rank asked for, 1 .. kLoveMaxRank (the iterations stop at min(rank, live rows))
+    double inv_ell2, sf2, sn2;
+    // scratch of the GP: Q transposed [kLoveMaxRank][ld], v [ld], the inert mask [ld], the parts of alpha_j
+    // [ld / 16], of Q^T v (two buffers, [ceil(ld / 64)][256] each), of |v|^2 [ceil(ld / 64)] and of the live-row
+    // count [ceil(ld / 256)], alpha, beta, the bidiagonal factor's diagonal and subdiagonal [kLoveMaxRank] each
+    // and the state words (kLove* below)
+    double* qt;
+    double* v;
+    int32_t* mask;
+    double* apart;
+    double* cpa;
+    double* cpb;
+    double* npart;
+    double* ipart;
+    double* alpha;
+    double* beta;
+    double* cd;
+    double* lsub;
+    int32_t* state;
+};
+// The state words: finished (kernels queued later do nothing), the root's rank m, 1 when every pivot was finite
+// and positive, the iteration cap min(rank, live rows), the live rows
+enum : int { kLoveDone = 0, kLoveM = 1, kLoveOk = 2, kLoveKmax = 3, kLoveLive = 4, kLoveInts = 8 };
+
+// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip, gp_refactor.hip, gp_fit.hip, gp_love.hip; what
+// the last five share, the tile pack's layout included, is in gp_tile.h).
 hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream);
 hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream);
 hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream);
@@ -388,6 +424,11 @@ hipError_t launch_gp_fit_eval(const GPFit& f, double* out, hipStream_t stream);
 // `a`, evaluate, Adam step with the early-stop rule; hist: [max_iter][4] or null, row = the step taken)
 hipError_t launch_gp_fit_init(double* state, const double* raw, hipStream_t stream);
 hipError_t launch_gp_fit_iteration(const GPRefactor& a, const GPFit& f, double lr, double* hist_dev, hipStream_t stream);
+// The LOVE root: the state, mask, Khat and q_0; iteration j (six launches; nothing once the state says done);
+// the root R [npad][rp] of rank m from the finished state (R is zeroed first)
+hipError_t launch_gp_love_begin(const GPLove& a, hipStream_t stream);
+hipError_t launch_gp_love_iteration(const GPLove& a, int j, hipStream_t stream);
+hipError_t launch_gp_love_root(const GPLove& a, int m, double* R, int rp, hipStream_t stream);
 // count < 0: the whole batch; else ranks first .. first + count - 1 of order[] (launch_sqp_order)
 hipError_t launch_sqp(const ProblemDev& P, const StateDev& S, const StepIO& io, int batch, hipStream_t stream,
                       int first = 0, int count = -1);

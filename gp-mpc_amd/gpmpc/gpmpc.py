@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .gp import GaussianProcess, fit_gp
+from .gp import LOVE_CHOLESKY_ROWS, GaussianProcess, fit_gp
 from .models import ModelSpec, get_spec
 from .mpc import MPC
 from .solver import BatchSolver, STATUS_NAMES, inverse_cdf, setup_prior_dynamics
@@ -31,6 +31,9 @@ class GPMPC:
 
     # the reference's quadrotor hover input (`gpmpc/gpmpc.py:18`); an instance's U_EQ is its model's
     U_EQ: np.ndarray = np.array([0.3234, 0, 0, 0])
+    # tightening variance mode: the constructor sets it ("love" unless told otherwise); a controller put
+    # together without the constructor has no LOVE roots to look after (_update_gps)
+    variance: str = "exact"
 
     def __init__(self, symbolic_model, traj: np.ndarray | None = None, prior_params: dict | None = None,
                  horizon: int = 25, q_mpc: list | None = None, r_mpc: list | None = None, sparse_gp: bool = False,
@@ -187,12 +190,36 @@ class GPMPC:
         self.gaussian_process = gps
         self._requires_recompile = True
 
+    def _update_gps(self, update):
+        """Run a device-side update of the handle's GPs (``update()``, whose result is returned) under
+        the controller's variance mode.  The updates refuse a GP with a LOVE root installed, which
+        belongs to the old training set or factor, so with ``variance="love"`` the roots are dropped
+        first and afterwards every GP with more than ``LOVE_CHOLESKY_ROWS`` rows gets a root built on
+        the device (``BatchSolver.love_root_gp``, which synchronises the stream); the others keep the
+        exact variance, as ``set_gps`` chooses for their size.  If the update raises, the GPs are left
+        on the exact variance."""
+        s = self.solver
+        love = self.variance == "love"
+        if love:
+            for g in range(self.model.n_gp):
+                if s.love_ranks[g] is not None:
+                    s.drop_love_root(g)
+        out = update()
+        if love:
+            for g in range(self.model.n_gp):
+                if s.gp_size(g)[0] > LOVE_CHOLESKY_ROWS:
+                    _, ok = s.love_root_gp(g, rank=s.love_rank)
+                    if not ok:
+                        raise _lib.GPMPCError(f"GP {g}: the LOVE root could not be built (a pivot was not positive); "
+                                              "the GP is on the exact variance")
+        return out
+
     def drop_oldest(self, m: int) -> list[torch.Tensor]:
         """Remove the ``m`` oldest training rows of every GP on the solver handle, on the device
         (``BatchSolver.drop_gp``, queued on the current stream, no refactorisation), and of the Python
         GP objects with them (``GaussianProcess.drop_oldest``).  At least one row stays.  Returns the
         status flags per GP (device tensors; a 0 means that GP must be uploaded again).  Not
-        available in sparse (FITC) mode, like ``append_data``."""
+        available in sparse (FITC) mode, like ``append_data``; LOVE roots as there."""
         if self.sparse:
             raise _lib.GPMPCError("drop_oldest: not available in sparse (FITC) mode")
         assert self.gaussian_process is not None and not self._requires_recompile, \
@@ -201,6 +228,9 @@ class GPMPC:
         n = self.solver.gp_size(0)[0]
         if not 1 <= m < n:   # before any GP changes, so the handle's GPs stay in step
             raise ValueError(f"drop_oldest: m must be 1..{n - 1} (at least one row stays), got {m}")
+        return self._update_gps(lambda: self._drop_oldest(m))
+
+    def _drop_oldest(self, m: int) -> list[torch.Tensor]:
         flags = []
         for i in range(len(self.gp_idx)):
             flags.append(self.solver.drop_gp(i, m))
@@ -215,6 +245,9 @@ class GPMPC:
         (``GaussianProcess.append_data``), so a later ``train_gp`` refit or upload sees all data.
         Returns the accepted flags per GP (device tensors).  Needs room (``gp_capacity``); not
         available in sparse (FITC) mode, whose inducing weights belong to the old training set.
+        With ``variance="love"`` the LOVE roots follow the data: they are dropped before the update and
+        built again on the device afterwards for every GP above ``LOVE_CHOLESKY_ROWS`` rows
+        (``_update_gps``; that build synchronises the stream).
 
         ``evict_oldest=True`` makes the training set a sliding window: when the new rows would
         exceed the capacity, exactly the excess is dropped from the old end first
@@ -233,15 +266,19 @@ class GPMPC:
         if excess > 0 and (not evict_oldest or excess >= n):
             raise _lib.GPMPCError(f"append_data: capacity exceeded ({n} + {inputs.shape[0]} rows, capacity {cap}; "
                                   "construct GPMPC with gp_capacity)")
-        if excess > 0:
-            self.drop_oldest(excess)
-        flags = []
-        for i, idx in enumerate(self.gp_idx):
-            X = torch.tensor(inputs[:, idx], device=self.device)
-            y = torch.tensor(targets[:, i], device=self.device)
-            flags.append(self.solver.append_gp(i, X, y))
-            self.gaussian_process[i].append_data(X, y)
-        return flags
+
+        def update():
+            if excess > 0:
+                self._drop_oldest(excess)
+            flags = []
+            for i, idx in enumerate(self.gp_idx):
+                X = torch.tensor(inputs[:, idx], device=self.device)
+                y = torch.tensor(targets[:, i], device=self.device)
+                flags.append(self.solver.append_gp(i, X, y))
+                self.gaussian_process[i].append_data(X, y)
+            return flags
+
+        return self._update_gps(update)
 
     def refresh_gps(self, hyperparameters: list | None = None) -> list[torch.Tensor]:
         """Factorise every GP on the solver handle again from scratch, on the device
@@ -251,13 +288,16 @@ class GPMPC:
         object (``GaussianProcess.set_hyperparameters``); by default every GP keeps its own, and the
         call only sheds the rounding that appends and drops have accumulated.  Returns the status
         flags per GP (device tensors; a 0 means that GP must be uploaded again).  Same preconditions
-        as ``append_data``; not available in sparse (FITC) mode."""
+        as ``append_data``, LOVE roots rebuilt as there; not available in sparse (FITC) mode."""
         if self.sparse:
             raise _lib.GPMPCError("refresh_gps: not available in sparse (FITC) mode")
         assert self.gaussian_process is not None and not self._requires_recompile, \
             "GP model must be uploaded (call reset())"
         if hyperparameters is not None and len(hyperparameters) != len(self.gp_idx):
             raise ValueError(f"expected {len(self.gp_idx)} (lengthscale, outputscale, noise) triples")
+        return self._update_gps(lambda: self._refresh_gps(hyperparameters))
+
+    def _refresh_gps(self, hyperparameters: list | None) -> list[torch.Tensor]:
         flags = []
         for i, gp in enumerate(self.gaussian_process):
             hyp = (gp.lengthscale, gp.outputscale, gp.noise) if hyperparameters is None else \
@@ -276,7 +316,8 @@ class GPMPC:
         ``fit="device"``: ``BatchSolver.fit_gp`` per GP, from the Python GP's current raw parameters
         on the handle's own factor, inputs and scratch; the fitted raw parameters are written into the
         Python GP objects (a GP whose fit failed keeps its own) and one int32 device flag per GP is
-        returned, like ``refresh_gps``'.  Single rank only: the data-parallel fit stays the torch one."""
+        returned, like ``refresh_gps``'.  Single rank only: the data-parallel fit stays the torch one.
+        Either way LOVE roots are dropped first and rebuilt on the device afterwards (``_update_gps``)."""
         if self.sparse:
             raise _lib.GPMPCError("refit_hyperparameters: not available in sparse (FITC) mode")
         if fit not in ("torch", "device"):
@@ -290,16 +331,20 @@ class GPMPC:
             if size > 1:
                 raise _lib.GPMPCError("refit_hyperparameters: fit='device' runs on one rank (the data-parallel fit is "
                                       "fit='torch')")
-            flags = []
-            for i, gp in enumerate(self.gaussian_process):
-                raw0 = [float(p) for p in gp.parameters()]
-                raw, _, ok = self.solver.fit_gp(i, gp.train_targets, raw0, lr, iterations)
-                if ok:
-                    for p, r in zip(gp.parameters(), raw):
-                        p.fill_(float(r))
-                    gp.K, gp.K_inv, gp._dev = None, None, None
-                flags.append(torch.tensor([ok], dtype=torch.int32, device=self.device))
-            return flags
+
+            def fit_all():
+                flags = []
+                for i, gp in enumerate(self.gaussian_process):
+                    raw0 = [float(p) for p in gp.parameters()]
+                    raw, _, ok = self.solver.fit_gp(i, gp.train_targets, raw0, lr, iterations)
+                    if ok:
+                        for p, r in zip(gp.parameters(), raw):
+                            p.fill_(float(r))
+                        gp.K, gp.K_inv, gp._dev = None, None, None
+                    flags.append(torch.tensor([ok], dtype=torch.int32, device=self.device))
+                return flags
+
+            return self._update_gps(fit_all)
         for gp in self.gaussian_process:
             if size > 1:
                 D.fit_gp_allreduce(gp, n_train=iterations, lr=lr)

@@ -138,7 +138,8 @@ class BatchSolver:
         if variance not in ("exact", "love"):
             raise ValueError("variance must be 'exact' or 'love'")
         self.love_ranks = [None] * self.spec.n_gp   # columns of each GP's LOVE root (None: exact)
-        self.love_roots = [None] * self.spec.n_gp   # the uploaded roots (host, float64), for checkers
+        self.love_roots = [None] * self.spec.n_gp   # the installed roots (host, float64), for checkers
+        self.love_rank = int(love_rank)             # the rank later device-built roots ask for (GPMPC)
         if gps is None:
             _lib.check(self.lib.gpmpc_use_gp(self._h, 0))
             self.gps = None
@@ -274,6 +275,47 @@ class BatchSolver:
         if hist is None:
             return raw, iters.value, ok.value
         return raw, iters.value, ok.value, (hist if isinstance(history, torch.Tensor) else hist[:iters.value].cpu().numpy())
+
+    def love_root_gp(self, gp_id: int, rank: int = 100, seed: int = 0, start=None) -> tuple[int, int]:
+        """Build the LOVE variance root of the handle's GP ``gp_id`` on the device and install it
+        (gpmpc_gp_love_root): Lanczos with full reorthogonalisation on k(X, X) + noise I, generated from
+        the handle's own rows and current hyperparameters, so it follows appends, drops and refits
+        without an upload.  The start vector is the seeded ``torch.randn`` draw of
+        ``GaussianProcess.love_root(rank, seed)`` over the GP's n current rows (inert rows included),
+        or ``start`` (n,); entries of inert rows are ignored.  The call synchronises the current
+        stream.  Returns ``(rank, ok)``: the installed root's rank (at most ``min(rank, live rows)``)
+        and 1, or ``(0, 0)`` with the handle, ``love_ranks`` and ``love_roots`` unchanged.  Needs
+        ``reserve_gp``; a root already installed is replaced."""
+        n = self.gp_size(gp_id)[0]
+        if start is None:
+            gen = torch.Generator(device="cpu").manual_seed(int(seed))
+            start = torch.randn(n, dtype=torch.float64, generator=gen)
+        q0 = torch.as_tensor(start).to(self.device, torch.float64).reshape(-1).contiguous()
+        if q0.shape[0] != n:
+            raise ValueError(f"GP {gp_id} has {n} training rows, got a start vector of {q0.shape[0]}")
+        r, ok = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(self.lib.gpmpc_gp_love_root(self._h, int(gp_id), int(rank), q0.data_ptr(), ctypes.byref(r),
+                                               ctypes.byref(ok), self._stream()))
+        if ok.value:
+            self.love_ranks[int(gp_id)] = r.value
+            self.love_roots[int(gp_id)] = self.variance_root(gp_id)
+        return r.value, ok.value
+
+    def variance_root(self, gp_id: int) -> np.ndarray:
+        """The LOVE root installed for the handle's GP ``gp_id``, read back from the device
+        (gpmpc_get_gp_variance_root): float64 (n, r); the library refuses when none is installed."""
+        n, r = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(self.lib.gpmpc_get_gp_variance_root(self._h, int(gp_id), ctypes.byref(n), ctypes.byref(r), None, None))
+        R = torch.empty(n.value, r.value, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.gpmpc_get_gp_variance_root(self._h, int(gp_id), None, None, R.data_ptr(), self._stream()))
+        return R.cpu().numpy()
+
+    def drop_love_root(self, gp_id: int):
+        """Back to the exact tightening variance for the handle's GP ``gp_id``
+        (gpmpc_set_gp_variance_root with R = NULL): what the device-side updates ask for first."""
+        _lib.check(self.lib.gpmpc_set_gp_variance_root(self._h, int(gp_id), 0, 0, None))
+        self.love_ranks[int(gp_id)] = None
+        self.love_roots[int(gp_id)] = None
 
     def gp_size(self, gp_id: int) -> tuple[int, int]:
         """(training rows, capacity) of the handle's GP ``gp_id`` (gpmpc_gp_size)."""

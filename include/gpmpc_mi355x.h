@@ -120,7 +120,8 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity);
  * the old weights are left alone and the row count advances either way.
  * Refused, with the GP unchanged: n + m above the capacity (GPMPC_ERR_ARG); GP not set, set
  * without Linv, a FITC upload (Xv != X), or a LOVE root installed -- it belongs to the old
- * training set, drop it first with gpmpc_set_gp_variance_root(R = NULL) (GPMPC_ERR_STATE). */
+ * training set, drop it first with gpmpc_set_gp_variance_root(R = NULL), or rebuild it afterwards with
+ * gpmpc_gp_love_root (GPMPC_ERR_STATE). */
 gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const double* Xnew_dev,
                              const double* ynew_dev, int32_t* accepted_dev, void* stream);
 
@@ -138,8 +139,8 @@ gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const do
  * gpmpc_set_gp before it is used.
  * Refused, with the GP unchanged: m < 1 or m >= n, at least one row stays (GPMPC_ERR_ARG); GP not
  * set, set without Linv, a FITC upload (Xv != X), a LOVE root installed (drop it first with
- * gpmpc_set_gp_variance_root(R = NULL)), or no gpmpc_gp_reserve since gpmpc_set_gp -- the update
- * writes the factor into the second buffer a reserve allocates (GPMPC_ERR_STATE). */
+ * gpmpc_set_gp_variance_root(R = NULL), or rebuild it afterwards with gpmpc_gp_love_root), or no
+ * gpmpc_gp_reserve since gpmpc_set_gp -- the update writes the factor into the second buffer a reserve allocates (GPMPC_ERR_STATE). */
 gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int32_t* ok_dev, void* stream);
 
 /* Factorise GP gp_id again from scratch on `stream`, from what the device already holds: the
@@ -160,8 +161,8 @@ gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int
  * is accessed out of bounds): upload it again with gpmpc_set_gp before it is used.
  * Refused, with the GP unchanged: y_dev NULL or a hyperparameter that is not finite and positive
  * (GPMPC_ERR_ARG); GP not set, set without Linv, a FITC upload (Xv != X), a LOVE root installed
- * (drop it first with gpmpc_set_gp_variance_root(R = NULL)), or no gpmpc_gp_reserve since
- * gpmpc_set_gp -- the work space is the second factor buffer and scratch a reserve allocates
+ * (drop it first with gpmpc_set_gp_variance_root(R = NULL), or rebuild it afterwards with
+ * gpmpc_gp_love_root), or no gpmpc_gp_reserve since gpmpc_set_gp -- the work space is the second factor buffer and scratch a reserve allocates
  * (GPMPC_ERR_STATE). */
 gpmpc_status gpmpc_gp_refactor(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double lengthscale,
                                double outputscale, double noise, int32_t* ok_dev, void* stream);
@@ -174,7 +175,8 @@ gpmpc_status gpmpc_gp_refactor(gpmpc_handle* h, int32_t gp_id, const double* y_d
  * log det from the diagonal of (L^-1)^T, alpha from the rows, K^-1 = L^-T L^-1 tile by tile on f64 MFMA
  * for tr((alpha alpha^T - K^-1) dK/dtheta).  After appends and drops it is the likelihood of the factor
  * as it has drifted.  Asynchronous, nothing read back; nothing of the GP changes.
- * Refused: y_dev or out_dev NULL (GPMPC_ERR_ARG); every state refusal of gpmpc_gp_refactor
+ * Refused: y_dev or out_dev NULL (GPMPC_ERR_ARG); every state refusal of gpmpc_gp_refactor, an installed
+ * LOVE root among them (drop it first, or rebuild it afterwards with gpmpc_gp_love_root)
  * (GPMPC_ERR_STATE; gpmpc_gp_reserve also allocates this call's scratch). */
 gpmpc_status gpmpc_gp_mll(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double* out_dev, void* stream);
 
@@ -194,9 +196,38 @@ gpmpc_status gpmpc_gp_mll(gpmpc_handle* h, int32_t gp_id, const double* y_dev, d
  * is left as passed in, and the GP is refactorised at the hyperparameters it had; if that
  * refactorisation fails too (the targets), its contents are unspecified as after gpmpc_gp_refactor's 0.
  * Refused, with the GP unchanged: y_dev or raw NULL, a raw value or lr that is not finite, lr <= 0,
- * max_iter < 1 (GPMPC_ERR_ARG); every state refusal of gpmpc_gp_refactor (GPMPC_ERR_STATE). */
+ * max_iter < 1 (GPMPC_ERR_ARG); every state refusal of gpmpc_gp_refactor, an installed LOVE root among
+ * them (drop it first, or rebuild it afterwards with gpmpc_gp_love_root) (GPMPC_ERR_STATE). */
 gpmpc_status gpmpc_gp_fit(gpmpc_handle* h, int32_t gp_id, const double* y_dev, double lr, int32_t max_iter, double* raw,
                           int32_t* iters_out, int32_t* ok_out, double* hist_dev, void* stream);
+
+/* Build the LOVE variance root of GP gp_id on the device and install it, as
+ * gpmpc_set_gp_variance_root would install the host's: Lanczos with full reorthogonalisation (two
+ * passes) on Khat = k(X, X) + noise I, generated on the device from the handle's own rows and current
+ * hyperparameters, from the start vector q0_dev [n] (device, float64; the library draws no random
+ * numbers).  It restates GaussianProcess.love_root (gpmpc/gp.py), its breakdown rule
+ * |v| <= 1e-12 max |alpha| included, up to the last step: instead of the eigendecomposition of the
+ * tridiagonal matrix T the root is R = Q C^-T with T = C C^T, C lower bidiagonal -- R R^T = Q T^-1 Q^T
+ * is the same matrix, and only it reaches the variance (csrc/gp_love.hip).  The root's rank is at most
+ * min(rank, live rows), 1 <= rank <= 256.  Inert rows (rejected append blocks, recognised by the zero
+ * on the factor's diagonal) take no part: their q0_dev entries are never read into a sum and may be
+ * anything, NaN included, and their rows of the root are exact zeros.  The result depends on the inputs
+ * alone, bit for bit (every sum has a fixed order).
+ * THE CALL SYNCHRONISES `stream` (the host needs the final rank).  rank_out, ok_out: host, may be
+ * NULL; the installed root's rank and 1, or 0 and 0 when a pivot of C was not finite and positive (or no
+ * row is live): then the handle is unchanged, a root installed before included.
+ * Refused, with the GP unchanged: q0_dev NULL or rank outside 1..256 (GPMPC_ERR_ARG); GP not set, set
+ * without Linv, a FITC upload (Xv != X), or no gpmpc_gp_reserve since gpmpc_set_gp -- Khat is built in
+ * the second factor buffer and the Lanczos vectors in scratch a reserve allocates (GPMPC_ERR_STATE).
+ * An installed root is no obstacle: it is replaced on success. */
+gpmpc_status gpmpc_gp_love_root(gpmpc_handle* h, int32_t gp_id, int32_t rank, const double* q0_dev,
+                                int32_t* rank_out, int32_t* ok_out, void* stream);
+
+/* The installed LOVE root of GP gp_id: its rows n (the variance GP's training rows) and its rank r,
+ * either may be NULL; with R_dev non-NULL (device, float64 [n][r] row-major, unpadded) the root is
+ * copied on `stream`.  GPMPC_ERR_STATE when no root is installed. */
+gpmpc_status gpmpc_get_gp_variance_root(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* r,
+                                        double* R_dev, void* stream);
 
 /* Training rows of GP gp_id (inert rows included) and its capacity; either may be NULL. */
 gpmpc_status gpmpc_gp_size(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* capacity);
