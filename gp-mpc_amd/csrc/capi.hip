@@ -69,12 +69,16 @@ struct GPSlot {
     double* love = nullptr;        // Lanczos vectors, partial sums and state of gpmpc_gp_love_root
     double* vroot = nullptr;       // LOVE root (tightening only), its padded columns and its rank
     int vroot_cols = 0, vroot_rank = 0;
+    // FITC mean built by gpmpc_gp_fitc, an overlay on the exact mean: its rows, tile pack and indices (FitcOut) and
+    // its inducing rows (0: none installed, the buffer is spare); the work space and the sizes it was allocated for
+    double *fitc = nullptr, *fitc_ws = nullptr;
+    int fitc_M = 0, fitc_ws_m = 0, fitc_ws_c = 0;
     // The slot's device buffers: the kReserved ones gpmpc_gp_reserve replaces, then the others
-    static constexpr int kReserved = 9, kBuffers = 11;
+    static constexpr int kReserved = 9, kBuffers = 13;
     static constexpr double* GPSlot::*kBuffer[kBuffers] = {&GPSlot::rows,  &GPSlot::tiles, &GPSlot::linvT,
                                                             &GPSlot::linvT_alt, &GPSlot::app, &GPSlot::drp,
                                                             &GPSlot::rfc, &GPSlot::fit, &GPSlot::love, &GPSlot::vrows,
-                                                            &GPSlot::vroot};
+                                                            &GPSlot::vroot, &GPSlot::fitc, &GPSlot::fitc_ws};
     hipError_t release(int count) {   // frees and clears the first `count` of them; returns the first error
         hipError_t first = hipSuccess;
         for (int i = 0; i < count; ++i) {
@@ -117,6 +121,17 @@ struct LoveLayout {
               cpa = apart + c / 16, cpb = cpa + 256 * nbo, npart = cpb + 256 * nbo, ipart = npart + nbo, alpha = ipart + nb,
               beta = alpha + kLoveMaxRank, cd = beta + kLoveMaxRank, lsub = cd + kLoveMaxRank, state = lsub + kLoveMaxRank,
               end = state + kLoveInts / 2;
+};
+// gpmpc_gp_fitc's work space for m (padded) inducing rows of a GP with a capacity of c (padded) rows: K_ss / B and
+// the two inverse factors [m][m] each | L_kk^-1 [m/16][256] | Gamma^-1, Gamma^-1 y [c] each | u, p, q [m] each | the
+// inert mask [c] and the padding mask [m] int32 | status word
+struct FitcLayout {
+    size_t m, c, A = 0, lt1 = m * m, lt2 = 2 * m * m, dinv = 3 * m * m, ginv = dinv + 16 * m, t = ginv + c, u = t + c,
+              p = u + m, q = p + m, lmask = q + m, smask = lmask + c / 2, flag = smask + m / 2, end = flag + 1;
+};
+// what it installs: rows [m][4] | tX, tW [m/16][64] each | the indices [m] int32
+struct FitcOut {
+    size_t m, rows = 0, tX = 4 * m, tW = 8 * m, idx = 12 * m, end = idx + m / 2;
 };
 constexpr bool layouts_hold(size_t c) {
     return AppendLayout{c}.end == 16 * c + c + 256 + 16 + 1 && AppendLayout{c}.flag == 17 * c + 272 &&
@@ -516,8 +531,9 @@ gpmpc_status gpmpc_set_gp(gpmpc_handle* h, int32_t gp_id, int32_t n, int32_t d, 
         for (int j = 0; j < 4; ++j) tW[tile_w_at(sl, j)] = wv[j];
     }
     GPSlot& gs = h->gp[gp_id];
-    HIPCHK(gs.release(GPSlot::kBuffers));   // (a LOVE root belongs to the previous training set)
+    HIPCHK(gs.release(GPSlot::kBuffers));   // (a LOVE root and a FITC mean belong to the previous training set)
     gs.vroot_cols = gs.vroot_rank = 0;
+    gs.fitc_M = gs.fitc_ws_m = gs.fitc_ws_c = 0;
     HIPCHK(hipMalloc(&gs.rows, rows.size() * sizeof(double)));
     HIPCHK(hipMemcpy(gs.rows, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMalloc(&gs.tiles, tiles.size() * sizeof(double)));
@@ -560,6 +576,7 @@ gpmpc_status gpmpc_set_gp(gpmpc_handle* h, int32_t gp_id, int32_t n, int32_t d, 
 struct GPUpdate {
     const char *verb, *takes, *root_of;
     double* GPSlot::*scratch;
+    bool keeps_fitc = false;   // a FITC mean built by gpmpc_gp_fitc is no obstacle (the others change what it was built from)
 };
 static const GPUpdate kAppend{"append", "takes appended rows", "the old training set", nullptr};
 static const GPUpdate kDrop{"drop", "drops rows", "the old training set", &GPSlot::drp};
@@ -567,7 +584,8 @@ static const GPUpdate kRefactor{"refactor", "is refactorised", "the old factor",
 static const GPUpdate kMll{"the likelihood", "has its likelihood evaluated", "the old factor", &GPSlot::fit};
 static const GPUpdate kFit{"fit", "is fitted", "the old factor", &GPSlot::fit};
 // (root_of null: an installed root is no obstacle, the call replaces it)
-static const GPUpdate kLove{"the LOVE root", "has its LOVE root built", nullptr, &GPSlot::love};
+static const GPUpdate kLove{"the LOVE root", "has its LOVE root built", nullptr, &GPSlot::love, true};
+static const GPUpdate kFitc{"the FITC mean", "has its FITC mean built", nullptr, &GPSlot::rfc, true};
 
 // What the three updates ask first, in this order (bad_args: what is wrong with the call's own arguments, or
 // null).  gpmpc_gp_reserve asks the same up to the exact upload (factor = false).
@@ -579,6 +597,9 @@ static gpmpc_status gp_update_ready(gpmpc_handle* h, int gp_id, const GPUpdate& 
     const GPSlot& gs = h->gp[gp_id];
     if (!gs.set) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
     if (!gs.exact) return fail(GPMPC_ERR_STATE, std::string("FITC upload (Xv != X): only an exact GP ") + op.takes);
+    if (gs.fitc_M && !op.keeps_fitc)
+        return fail(GPMPC_ERR_STATE, "a FITC mean is installed: it belongs to the old training set (drop it first, "
+                                     "gpmpc_gp_fitc with M = 0, or rebuild it afterwards)");
     if (!factor) return GPMPC_OK;
     if (!gs.linvT) return fail(GPMPC_ERR_STATE, std::string(op.verb) + " needs Linv (the GP was set without it)");
     if (gs.vroot && op.root_of)
@@ -646,7 +667,8 @@ gpmpc_status gpmpc_gp_size(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* 
     if (!h) return fail(GPMPC_ERR_ARG, "null handle");
     if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
     if (!h->gp[gp_id].set) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
-    if (n) *n = h->P.gp[gp_id].n;
+    // (an exact GP's training rows are its variance rows, whether or not a FITC mean overlays the exact one)
+    if (n) *n = h->gp[gp_id].exact ? h->P.gp[gp_id].nv : h->P.gp[gp_id].n;
     if (capacity) *capacity = h->gp[gp_id].cap;
     return GPMPC_OK;
 }
@@ -984,7 +1006,7 @@ gpmpc_status gpmpc_gp_love_root(gpmpc_handle* h, int32_t gp_id, int32_t rank, co
     a.A = gs.linvT_alt;
     a.q0 = q0_dev;
     a.npad = gs.npad;
-    a.n = g.n;
+    a.n = g.nv;   // (the training rows: g.n counts the inducing rows under a FITC mean)
     a.ld = cpad;
     a.rank = rank;
     a.inv_ell2 = g.inv_ell2;
@@ -1006,7 +1028,7 @@ gpmpc_status gpmpc_gp_love_root(gpmpc_handle* h, int32_t gp_id, int32_t rank, co
     HIPCHK(launch_gp_love_begin(a, s));
     // the done word is read back once per kLoveQueue iterations; what is queued past the stop changes nothing
     constexpr int kLoveQueue = 8;
-    const int iters = std::min(rank, g.n);
+    const int iters = std::min(rank, a.n);
     int32_t st[kLoveInts] = {0};
     for (int done = 0; done < iters && !st[kLoveDone];) {
         const int q = std::min(kLoveQueue, iters - done);
@@ -1056,6 +1078,130 @@ gpmpc_status gpmpc_get_gp_variance_root(gpmpc_handle* h, int32_t gp_id, int32_t*
     const size_t wb = (size_t)gs.vroot_rank * sizeof(double);
     HIPCHK(hipMemcpy2DAsync(R_dev, wb, gs.vroot, (size_t)gs.vroot_cols * sizeof(double), wb, rows,
                             hipMemcpyDeviceToDevice, s));
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_fitc(gpmpc_handle* h, int32_t gp_id, int32_t M, const int32_t* idx_dev, const double* y_dev,
+                           double jitter, int32_t* ok_out, void* stream) {
+    const char* bad = nullptr;
+    if (M < 0) bad = "M must be 0 (remove the FITC mean) or 1 .. n";
+    else if (M == 0 && idx_dev) bad = "M = 0 removes the FITC mean and takes no indices (idx_dev must be NULL)";
+    else if (M >= 1 && (!idx_dev || !y_dev)) bad = "no indices or no targets";
+    else if (M >= 1 && !(std::isfinite(jitter) && jitter >= 0.0)) bad = "jitter must be finite and not negative";
+    const gpmpc_status ready = gp_update_ready(h, gp_id, kFitc, bad);
+    if (ready != GPMPC_OK) return ready;
+    GPSlot& gs = h->gp[gp_id];
+    GPDev& g = h->P.gp[gp_id];
+    const int n = g.nv;
+    if (M > n) return fail(GPMPC_ERR_ARG, "M must be 1 .. n: " + std::to_string(M) + " inducing rows of " +
+                                              std::to_string(n) + " training rows asked for");
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const int cpad = (gs.cap + 15) / 16 * 16;
+    if (M == 0) {   // back to the exact mean (the overlay's buffer stays as a spare: nothing is freed under queued work)
+        if (!gs.fitc_M) return GPMPC_OK;
+        g.rows = gs.rows;
+        g.tX = gs.tiles;
+        g.tW = gs.tiles + (size_t)(cpad / 16) * 64;
+        g.n = n;
+        g.ntile = (n + 15) / 16;
+        gs.fitc_M = 0;
+        bump_lin(h);
+        return GPMPC_OK;
+    }
+    if (ok_out) *ok_out = 0;
+    const int mpad = (M + 15) / 16 * 16;
+    if (!gs.fitc_ws || gs.fitc_ws_m < mpad || gs.fitc_ws_c < cpad) {
+        double* ws = nullptr;
+        if (hipMalloc(&ws, FitcLayout{(size_t)mpad, (size_t)cpad}.end * sizeof(double)) != hipSuccess)
+            return fail(GPMPC_ERR_NOMEM, "gpmpc_gp_fitc: no memory for the work space of " + std::to_string(M) + " inducing rows");
+        if (gs.fitc_ws) (void)hipFree(gs.fitc_ws);   // (every earlier build has synchronised: nothing reads it)
+        gs.fitc_ws = ws;
+        gs.fitc_ws_m = mpad;
+        gs.fitc_ws_c = cpad;
+    }
+    // staged in a local buffer: the handle's mean changes on success only
+    const FitcOut out{(size_t)mpad};
+    double* buf = nullptr;
+    if (hipMalloc(&buf, out.end * sizeof(double)) != hipSuccess)
+        return fail(GPMPC_ERR_NOMEM, "gpmpc_gp_fitc: no memory for " + std::to_string(M) + " inducing rows");
+    const FitcLayout lay{(size_t)mpad, (size_t)cpad};
+    GPFitc a{};
+    a.rows = gs.rows;
+    a.linvT = gs.linvT;
+    a.y = y_dev;
+    a.idx = idx_dev;
+    a.V = gs.linvT_alt;
+    a.npad = gs.npad;
+    a.n = n;
+    a.mpad = mpad;
+    a.M = M;
+    a.d = h->md.gp_dim[gp_id];
+    for (int k = 0; k < 3; ++k) a.xbar[k] = g.xbar[k];
+    a.inv_ell2 = g.inv_ell2;
+    a.sf2 = g.sf2;
+    a.sn2 = g.sn2;
+    a.jitter = jitter;
+    double* ws = gs.fitc_ws;
+    a.A = ws + lay.A;
+    a.lt1 = ws + lay.lt1;
+    a.lt2 = ws + lay.lt2;
+    a.dinv = ws + lay.dinv;
+    a.ginv = ws + lay.ginv;
+    a.t = ws + lay.t;
+    a.u = ws + lay.u;
+    a.p = ws + lay.p;
+    a.q = ws + lay.q;
+    a.lmask = reinterpret_cast<int32_t*>(ws + lay.lmask);
+    a.smask = reinterpret_cast<int32_t*>(ws + lay.smask);
+    a.flag = reinterpret_cast<int32_t*>(ws + lay.flag);
+    a.srows = buf + out.rows;
+    a.stX = buf + out.tX;
+    a.stW = buf + out.tW;
+    a.sidx = reinterpret_cast<int32_t*>(buf + out.idx);
+    int32_t flag = 0;
+    hipError_t e = launch_gp_fitc(a, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, a.flag, sizeof(flag), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipFree(buf);
+        return fail(GPMPC_ERR_HIP, std::string("FITC mean: ") + hipGetErrorString(e));
+    }
+    if (flag != 1) {   // (the handle's mean, exact or FITC, stays)
+        (void)hipFree(buf);
+        return GPMPC_OK;
+    }
+    if (gs.fitc) (void)hipFree(gs.fitc);   // (the stream is drained, and every other stream's work was ordered before it)
+    gs.fitc = buf;
+    gs.fitc_M = M;
+    g.rows = a.srows;
+    g.tX = a.stX;
+    g.tW = a.stW;
+    g.n = M;
+    g.ntile = mpad / 16;
+    bump_lin(h);
+    if (ok_out) *ok_out = 1;
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_get_gp_fitc(gpmpc_handle* h, int32_t gp_id, int32_t* M, int32_t* idx_dev, double* w_dev, void* stream) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    if (gp_id < 0 || gp_id >= h->md.ngp) return fail(GPMPC_ERR_ARG, "gp_id out of range");
+    const GPSlot& gs = h->gp[gp_id];
+    const int m = gs.set ? gs.fitc_M : 0;
+    if (M) *M = m;
+    if (m == 0 || (!idx_dev && !w_dev)) return GPMPC_OK;
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const FitcOut out{(size_t)((m + 15) / 16 * 16)};
+    if (idx_dev) HIPCHK(hipMemcpyAsync(idx_dev, gs.fitc + out.idx, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (w_dev)
+        HIPCHK(hipMemcpy2DAsync(w_dev, sizeof(double), gs.fitc + out.rows + 3, 4 * sizeof(double), sizeof(double), m,
+                                hipMemcpyDeviceToDevice, s));
     return GPMPC_OK;
 }
 

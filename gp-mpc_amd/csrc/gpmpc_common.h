@@ -406,8 +406,46 @@ struct GPLove {
 // and positive, the iteration cap min(rank, live rows), the live rows
 enum : int { kLoveDone = 0, kLoveM = 1, kLoveOk = 2, kLoveKmax = 3, kLoveLive = 4, kLoveInts = 8 };
 
-// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip, gp_refactor.hip, gp_fit.hip, gp_love.hip; what
-// the last five share, the tile pack's layout included, is in gp_tile.h).
+// The FITC inducing-point mean of an exact GP built on the device (gp_fitc.hip; gpmpc_gp_fitc fills it): the
+// weights of the M inducing rows S = X[idx] from the training rows, the targets and the current hyperparameters.
+// Nothing of the GP is written through it: the result goes to staged rows and tiles the caller installs.
+struct GPFitc {
+    const double* rows;   // [>= npad][4], the training rows (the slot's exact rows): the inputs
+    const double* linvT;  // [npad][npad], the live factor (a zero on its diagonal: an inert or padding row)
+    const double* y;      // [n] targets in row order (device); inert rows' entries are not read into sums
+    const int32_t* idx;   // [M] the inducing rows' indices (device)
+    double* V;            // [mpad][npad] work space (the second factor buffer): L^-1 k(S, X)
+    int32_t npad;         // n rounded up to 16
+    int32_t n;
+    int32_t mpad;         // M rounded up to 16
+    int32_t M;
+    int32_t d;
+    double xbar[3];       // the tile pack's centre (the GP's own)
+    double inv_ell2, sf2, sn2, jitter;
+    // work space of the call: K_ss + jitter I and L, then B and C [mpad][mpad]; (L^-1)^T and (C^-1)^T [mpad][mpad]
+    // each; the diagonal tiles' inverses [mpad/16][256]; Gamma^-1 and Gamma^-1 y [npad] each; u, p, q [mpad] each;
+    // the inert mask of the training rows [npad], the padding mask of the inducing rows [mpad], the status
+    double* A;
+    double* lt1;
+    double* lt2;
+    double* dinv;
+    double* ginv;
+    double* t;
+    double* u;
+    double* p;
+    double* q;
+    int32_t* lmask;
+    int32_t* smask;
+    int32_t* flag;
+    // staged result: rows [mpad][4] (inputs, weight), tX, tW [mpad/16][64] each, the indices [mpad]
+    double* srows;
+    double* stX;
+    double* stW;
+    int32_t* sidx;
+};
+
+// Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip, gp_refactor.hip, gp_fit.hip, gp_love.hip,
+// gp_fitc.hip; what the last six share, the tile pack's layout included, is in gp_tile.h).
 hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream);
 hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream);
 hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream);
@@ -429,6 +467,8 @@ hipError_t launch_gp_fit_iteration(const GPRefactor& a, const GPFit& f, double l
 hipError_t launch_gp_love_begin(const GPLove& a, hipStream_t stream);
 hipError_t launch_gp_love_iteration(const GPLove& a, int j, hipStream_t stream);
 hipError_t launch_gp_love_root(const GPLove& a, int m, double* R, int rp, hipStream_t stream);
+// The FITC mean: everything from the status word set to 1 to the staged rows and tiles (the caller reads the status)
+hipError_t launch_gp_fitc(const GPFitc& a, hipStream_t stream);
 // count < 0: the whole batch; else ranks first .. first + count - 1 of order[] (launch_sqp_order)
 hipError_t launch_sqp(const ProblemDev& P, const StateDev& S, const StepIO& io, int batch, hipStream_t stream,
                       int first = 0, int count = -1);

@@ -21,7 +21,7 @@ LIB_PATH = Path(os.environ.get("GPMPC_LIB", _DEFAULT_LIB))
 CSRC = Path(__file__).resolve().parents[1] / "csrc"
 # the files gpmpc_build_id's source hash covers, in the Makefile's order (HASHED)
 HASHED = ["sqp_kernel.hip", "gp_kernels.hip", "gp_append.hip", "gp_drop.hip", "gp_refactor.hip", "gp_fit.hip",
-          "gp_love.hip", "capi.hip", "gpmpc_common.h", "gp_tile.h", "models.h", "../../include/gpmpc_mi355x.h", "build_id.cpp", "Makefile"]
+          "gp_love.hip", "gp_fitc.hip", "capi.hip", "gpmpc_common.h", "gp_tile.h", "models.h", "../../include/gpmpc_mi355x.h", "build_id.cpp", "Makefile"]
 
 _lib = None
 
@@ -45,6 +45,8 @@ SIGNATURES = {
     "gpmpc_gp_fit": (_I, [_P, _I, _P, _D, _I, POINTER(_D), POINTER(_I), POINTER(_I), _P, _P]),
     "gpmpc_gp_love_root": (_I, [_P, _I, _I, _P, POINTER(_I), POINTER(_I), _P]),
     "gpmpc_get_gp_variance_root": (_I, [_P, _I, POINTER(_I), POINTER(_I), _P, _P]),
+    "gpmpc_gp_fitc": (_I, [_P, _I, _I, _P, _P, _D, POINTER(_I), _P]),
+    "gpmpc_get_gp_fitc": (_I, [_P, _I, POINTER(_I), _P, _P, _P]),
     "gpmpc_gp_size": (_I, [_P, _I, POINTER(_I), POINTER(_I)]),
     "gpmpc_use_gp": (_I, [_P, _I]),
     "gpmpc_set_gp_variance_root": (_I, [_P, _I, _I, _I, _P]),

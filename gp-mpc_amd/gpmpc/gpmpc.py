@@ -34,12 +34,19 @@ class GPMPC:
     # tightening variance mode: the constructor sets it ("love" unless told otherwise); a controller put
     # together without the constructor has no LOVE roots to look after (_update_gps)
     variance: str = "exact"
+    # where the sparse (FITC) mean is built: "host" (precompute_sparse_posterior_mean, uploaded once; no
+    # device-side update of the GPs) or "device" (BatchSolver.fitc_gp on the uploaded exact GPs, rebuilt after
+    # every update); the jitter the device build adds to the diagonal of K_ss; its last draw of inducing rows
+    fitc: str = "host"
+    fitc_jitter: float = 0.0
+    fitc_idx: np.ndarray | None = None
 
     def __init__(self, symbolic_model, traj: np.ndarray | None = None, prior_params: dict | None = None,
                  horizon: int = 25, q_mpc: list | None = None, r_mpc: list | None = None, sparse_gp: bool = False,
                  prob: float = 0.955, max_gp_samples: int = 30, seed: int = 1337, device: str = "cuda",
                  output_dir: Path | None = None, batch: int = 1, variance_inputs: str = "reference",
-                 variance: str = "love", gp_capacity: int | None = None, **solver_kw):
+                 variance: str = "love", gp_capacity: int | None = None, fitc: str = "host",
+                 fitc_jitter: float = 0.0, **solver_kw):
         spec = (symbolic_model if isinstance(symbolic_model, ModelSpec) else get_spec(symbolic_model)).copy()
         # "reference": the variance input map of `gpmpc/gpmpc.py:437-444` (for quad3d it indexes the
         # full state-input vector with the GP-input-space indices); "dynamics": each GP's own inputs
@@ -64,6 +71,13 @@ class GPMPC:
                 raise ValueError(f"GPMPC requires prior_params with keys {sorted(spec.prior)}; missing {missing}")
             spec.prior = {k: float(prior_params[k]) for k in spec.prior}
         self.sparse = sparse_gp
+        if fitc not in ("host", "device"):
+            raise ValueError("fitc must be 'host' or 'device'")
+        if fitc == "device" and not sparse_gp:
+            raise ValueError("fitc='device' builds the sparse (FITC) mean: it needs sparse_gp=True")
+        self.fitc = fitc
+        self.fitc_jitter = float(fitc_jitter)
+        self.fitc_idx = None
         self.output_dir = output_dir
         self.device = torch.device(device)
         self.dt = spec.dt
@@ -197,9 +211,18 @@ class GPMPC:
         first and afterwards every GP with more than ``LOVE_CHOLESKY_ROWS`` rows gets a root built on
         the device (``BatchSolver.love_root_gp``, which synchronises the stream); the others keep the
         exact variance, as ``set_gps`` chooses for their size.  If the update raises, the GPs are left
-        on the exact variance."""
+        on the exact variance.
+
+        With ``sparse_gp=True, fitc="device"`` the FITC means are handled the same way: dropped before the
+        update, which works on the exact GPs underneath, and built again afterwards from a fresh draw of
+        inducing rows over the current training rows (``_build_fitc``)."""
         s = self.solver
         love = self.variance == "love"
+        fitc = self.sparse and self.fitc == "device"
+        if fitc:
+            for g in range(self.model.n_gp):
+                if s.fitc_sizes[g]:
+                    s.drop_fitc(g)
         if love:
             for g in range(self.model.n_gp):
                 if s.love_ranks[g] is not None:
@@ -212,15 +235,31 @@ class GPMPC:
                     if not ok:
                         raise _lib.GPMPCError(f"GP {g}: the LOVE root could not be built (a pivot was not positive); "
                                               "the GP is on the exact variance")
+        if fitc:
+            self._build_fitc()
         return out
+
+    def _build_fitc(self):
+        """The FITC mean of every GP on the solver handle, built on the device (``BatchSolver.fitc_gp``) on one
+        draw of ``min(n, max_gp_samples)`` inducing rows over the handle's n current training rows: the
+        ``np_random.choice`` call of ``precompute_sparse_posterior_mean``, so the same seed gives the same
+        rows.  The draw is kept as ``fitc_idx``."""
+        s = self.solver
+        n = s.gp_size(0)[0]
+        self.fitc_idx = np.asarray(self.np_random.choice(range(n), size=min(n, self.max_gp_samples), replace=False))
+        for g, gp in enumerate(self.gaussian_process):
+            if not s.fitc_gp(g, self.fitc_idx, gp.train_targets, self.fitc_jitter):
+                hint = "; try fitc_jitter > 0" if self.fitc_jitter == 0.0 else ""
+                raise _lib.GPMPCError(f"GP {g}: the FITC mean could not be built (a pivot or a Gamma was not positive, "
+                                      f"or an inducing row is inert); the GP is on the exact mean{hint}")
 
     def drop_oldest(self, m: int) -> list[torch.Tensor]:
         """Remove the ``m`` oldest training rows of every GP on the solver handle, on the device
         (``BatchSolver.drop_gp``, queued on the current stream, no refactorisation), and of the Python
         GP objects with them (``GaussianProcess.drop_oldest``).  At least one row stays.  Returns the
-        status flags per GP (device tensors; a 0 means that GP must be uploaded again).  Not
-        available in sparse (FITC) mode, like ``append_data``; LOVE roots as there."""
-        if self.sparse:
+        status flags per GP (device tensors; a 0 means that GP must be uploaded again).  In sparse
+        (FITC) mode only with ``fitc="device"``, like ``append_data``; LOVE roots and FITC means as there."""
+        if self.sparse and self.fitc != "device":
             raise _lib.GPMPCError("drop_oldest: not available in sparse (FITC) mode")
         assert self.gaussian_process is not None and not self._requires_recompile, \
             "GP model must be uploaded (call reset())"
@@ -243,8 +282,10 @@ class GPMPC:
         ``preprocess_data`` returns them.  Every GP on the solver handle is extended on the device
         (``BatchSolver.append_gp``, queued on the current stream) and the Python GP objects with it
         (``GaussianProcess.append_data``), so a later ``train_gp`` refit or upload sees all data.
-        Returns the accepted flags per GP (device tensors).  Needs room (``gp_capacity``); not
-        available in sparse (FITC) mode, whose inducing weights belong to the old training set.
+        Returns the accepted flags per GP (device tensors).  Needs room (``gp_capacity``).  In
+        sparse (FITC) mode the inducing weights belong to the old training set: with ``fitc="host"`` the call
+        is not available; with ``fitc="device"`` the FITC means are dropped before the update and built again
+        on the device afterwards, on a fresh draw of inducing rows (``_update_gps``, ``fitc_idx``).
         With ``variance="love"`` the LOVE roots follow the data: they are dropped before the update and
         built again on the device afterwards for every GP above ``LOVE_CHOLESKY_ROWS`` rows
         (``_update_gps``; that build synchronises the stream).
@@ -252,7 +293,7 @@ class GPMPC:
         ``evict_oldest=True`` makes the training set a sliding window: when the new rows would
         exceed the capacity, exactly the excess is dropped from the old end first
         (``drop_oldest``).  Appending more rows than the capacity holds stays an error."""
-        if self.sparse:
+        if self.sparse and self.fitc != "device":
             raise _lib.GPMPCError("append_data: not available in sparse (FITC) mode")
         assert self.gaussian_process is not None and not self._requires_recompile, \
             "GP model must be uploaded (call reset())"
@@ -288,8 +329,9 @@ class GPMPC:
         object (``GaussianProcess.set_hyperparameters``); by default every GP keeps its own, and the
         call only sheds the rounding that appends and drops have accumulated.  Returns the status
         flags per GP (device tensors; a 0 means that GP must be uploaded again).  Same preconditions
-        as ``append_data``, LOVE roots rebuilt as there; not available in sparse (FITC) mode."""
-        if self.sparse:
+        as ``append_data``, LOVE roots and device-built FITC means rebuilt as there; in sparse (FITC) mode only with
+        ``fitc="device"``."""
+        if self.sparse and self.fitc != "device":
             raise _lib.GPMPCError("refresh_gps: not available in sparse (FITC) mode")
         assert self.gaussian_process is not None and not self._requires_recompile, \
             "GP model must be uploaded (call reset())"
@@ -317,8 +359,9 @@ class GPMPC:
         on the handle's own factor, inputs and scratch; the fitted raw parameters are written into the
         Python GP objects (a GP whose fit failed keeps its own) and one int32 device flag per GP is
         returned, like ``refresh_gps``'.  Single rank only: the data-parallel fit stays the torch one.
-        Either way LOVE roots are dropped first and rebuilt on the device afterwards (``_update_gps``)."""
-        if self.sparse:
+        Either way LOVE roots (and, with ``fitc="device"``, FITC means) are dropped first and rebuilt on the
+        device afterwards (``_update_gps``); in sparse (FITC) mode only with ``fitc="device"``."""
+        if self.sparse and self.fitc != "device":
             raise _lib.GPMPCError("refit_hyperparameters: not available in sparse (FITC) mode")
         if fit not in ("torch", "device"):
             raise ValueError("fit must be 'torch' or 'device'")
@@ -383,13 +426,16 @@ class GPMPC:
         if self._requires_recompile:
             assert self.gaussian_process is not None, "GP must be trained before reinitializing"
             fitc = None
-            if self.sparse:
+            device_fitc = self.sparse and self.fitc == "device"
+            if self.sparse and not device_fitc:
                 n = self.gaussian_process[0].train_targets.shape[0]
                 fitc = self.precompute_sparse_posterior_mean(min(n, self.max_gp_samples))
             self.solver.set_gps(self.gaussian_process, with_variance=True, fitc=fitc, variance=self.variance)
-            if self.gp_capacity is not None and not self.sparse:
+            if (self.gp_capacity is not None and not self.sparse) or device_fitc:
                 for g in range(self.model.n_gp):   # (a training set already past the capacity stays as uploaded)
-                    self.solver.reserve_gp(g, max(self.gp_capacity, self.solver.gp_size(g)[0]))
+                    self.solver.reserve_gp(g, max(self.gp_capacity or 0, self.solver.gp_size(g)[0]))
+            if device_fitc:   # the exact GPs are uploaded: their FITC means are built where they live
+                self._build_fitc()
             self._requires_recompile = False
             # new GPs: the reference builds a fresh AcadosOcpSolver (`gpmpc/gpmpc.py:97-108`), whose
             # memory -- iterate and multipliers -- starts from zero

@@ -140,6 +140,7 @@ class BatchSolver:
         self.love_ranks = [None] * self.spec.n_gp   # columns of each GP's LOVE root (None: exact)
         self.love_roots = [None] * self.spec.n_gp   # the installed roots (host, float64), for checkers
         self.love_rank = int(love_rank)             # the rank later device-built roots ask for (GPMPC)
+        self.fitc_sizes = [0] * self.spec.n_gp      # inducing rows of each GP's device-built FITC mean (0: none)
         if gps is None:
             _lib.check(self.lib.gpmpc_use_gp(self._h, 0))
             self.gps = None
@@ -316,6 +317,48 @@ class BatchSolver:
         _lib.check(self.lib.gpmpc_set_gp_variance_root(self._h, int(gp_id), 0, 0, None))
         self.love_ranks[int(gp_id)] = None
         self.love_roots[int(gp_id)] = None
+
+    def fitc_gp(self, gp_id: int, idx, y, jitter: float = 0.0) -> int:
+        """Build the FITC inducing-point mean of the handle's GP ``gp_id`` on the device and install it as the
+        mean the solver reads (gpmpc_gp_fitc): the weights of the inducing rows ``X[idx]`` (M distinct row
+        indices, 1 <= M <= n) from the handle's own training rows, its current hyperparameters and the
+        targets ``y`` (n,) of its n current rows (``gp_size``; inert rows' entries are ignored), with ``jitter``
+        added to the diagonal of K_ss (0: the reference's formula).  cuda or host tensors (or arrays), moved
+        to the device if needed; runs on the current stream and synchronises it.  The exact GP stays in the
+        handle beside the FITC mean: ``gp_size`` and the variance are unchanged.  Returns 1, or 0 with the
+        handle and ``fitc_sizes`` unchanged (a pivot or a Gamma not positive, a target not finite, an index
+        that names an inert row or lies outside 0 .. n-1).  Needs ``reserve_gp``; a FITC mean already
+        installed is replaced on success."""
+        idx = torch.as_tensor(idx).to(self.device, torch.int32).reshape(-1).contiguous()
+        y = self._targets(gp_id, y)
+        ok = ctypes.c_int32()
+        _lib.check(self.lib.gpmpc_gp_fitc(self._h, int(gp_id), int(idx.shape[0]), idx.data_ptr() if idx.numel() else None,
+                                          y.data_ptr() if y.numel() else None, float(jitter), ctypes.byref(ok),
+                                          self._stream()))
+        if ok.value:
+            self.fitc_sizes[int(gp_id)] = int(idx.shape[0])
+        return ok.value
+
+    def drop_fitc(self, gp_id: int):
+        """Back to the exact mean for the handle's GP ``gp_id`` (gpmpc_gp_fitc with M = 0): what the
+        device-side updates ask for first.  Queued on the current stream, no synchronisation."""
+        _lib.check(self.lib.gpmpc_gp_fitc(self._h, int(gp_id), 0, None, None, 0.0, None, self._stream()))
+        self.fitc_sizes[int(gp_id)] = 0
+
+    def fitc_size(self, gp_id: int) -> int:
+        """Inducing rows of the FITC mean ``fitc_gp`` installed for GP ``gp_id``, 0 when none is (gpmpc_get_gp_fitc)."""
+        m = ctypes.c_int32()
+        _lib.check(self.lib.gpmpc_get_gp_fitc(self._h, int(gp_id), ctypes.byref(m), None, None, None))
+        return m.value
+
+    def fitc_mean(self, gp_id: int) -> tuple[np.ndarray, np.ndarray]:
+        """(indices (M,) int32, weights (M,) float64) of the installed FITC mean, read back from the device."""
+        m = self.fitc_size(gp_id)
+        idx = torch.empty(m, dtype=torch.int32, device=self.device)
+        w = torch.empty(m, dtype=torch.float64, device=self.device)
+        if m:
+            _lib.check(self.lib.gpmpc_get_gp_fitc(self._h, int(gp_id), None, idx.data_ptr(), w.data_ptr(), self._stream()))
+        return idx.cpu().numpy(), w.cpu().numpy()
 
     def gp_size(self, gp_id: int) -> tuple[int, int]:
         """(training rows, capacity) of the handle's GP ``gp_id`` (gpmpc_gp_size)."""

@@ -229,7 +229,49 @@ gpmpc_status gpmpc_gp_love_root(gpmpc_handle* h, int32_t gp_id, int32_t rank, co
 gpmpc_status gpmpc_get_gp_variance_root(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* r,
                                         double* R_dev, void* stream);
 
-/* Training rows of GP gp_id (inert rows included) and its capacity; either may be NULL. */
+/* Build the FITC inducing-point mean of GP gp_id on the device and install it as the mean the solver reads,
+ * as gpmpc_set_gp(X = S, alpha = w, Xv = training rows) would: from the handle's own n training rows X
+ * (n as gpmpc_gp_size reports it, inert rows included), its current hyperparameters, the caller's device
+ * targets y_dev [n] (float64, in row order, as gpmpc_gp_refactor takes them) and the inducing rows
+ * S = X[idx], idx_dev [M] a device int32 array, 1 <= M <= n.  It restates gpmpc/gpmpc.py:392-397 in the
+ * factored form (csrc/gp_fitc.hip), jitter >= 0 an absolute value added to the diagonal of K_ss (0: the
+ * reference's own formula):
+ *   K_ss + jitter I = L L^T,  V = L^-1 k(S, X),  Gamma_i = outputscale + noise - |V[:, i]|^2,
+ *   B = I + V Gamma^-1 V^T = C C^T,  w = L^-T B^-1 V Gamma^-1 y
+ * so that the mean at z is sum_j w_j k(z, S_j), k carrying the outputscale.  Inert rows (rejected append
+ * blocks, recognised by the zero on the factor's diagonal) take no part: their Gamma^-1 is 0 and their
+ * y_dev entries are never read into a sum and may be anything, NaN included.  Distinct indices are the
+ * caller's responsibility (with jitter 0 a duplicate fails its pivot).  The result depends on the inputs
+ * alone, bit for bit (every sum has a fixed order).
+ * The FITC mean is an overlay on the exact GP, which stays in the handle beside it (rows with alpha, the
+ * tile pack, the factor, the capacity): gpmpc_gp_size keeps reporting the training rows,
+ * gpmpc_gp_predict / gpmpc_gp_mean_grad return the FITC mean with the exact variance, the tightening
+ * variance and a LOVE root are untouched.  The tile pack of the inducing rows is centred on the xbar the
+ * GP already has.  M = 0 with idx_dev = NULL removes the overlay and restores the exact mean (no
+ * synchronisation; y_dev, jitter and ok_out are ignored; M = 0 with idx_dev non-NULL is GPMPC_ERR_ARG).
+ * gpmpc_set_gp clears the overlay; gpmpc_set_gp_variance_root and gpmpc_gp_love_root leave it alone.
+ * While it is installed gpmpc_gp_append, _drop_oldest, _refactor, _mll, _fit and gpmpc_gp_reserve are
+ * refused (GPMPC_ERR_STATE): the overlay belongs to the old training set; drop it first with M = 0, or
+ * rebuild it afterwards.
+ * With M >= 1 THE CALL SYNCHRONISES `stream` (the host reads the status).  ok_out: host, may be NULL; 1
+ * on success, 0 when a pivot of L or C or a live row's Gamma is not finite and positive, a live target is
+ * not finite, or an index names an inert row or lies outside 0 .. n-1: then the handle is unchanged, a
+ * FITC mean installed before included.  The work space depends on M: the call allocates it and the handle
+ * keeps it for a later call of the same or a smaller M (GPMPC_ERR_NOMEM, handle unchanged, when it cannot).
+ * Refused, with the GP unchanged: y_dev or idx_dev NULL with M >= 1, M outside 1 .. n, jitter negative or
+ * not finite (GPMPC_ERR_ARG); GP not set, set without Linv, a FITC upload (Xv != X), or no
+ * gpmpc_gp_reserve since gpmpc_set_gp -- V is built in the second factor buffer (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_gp_fitc(gpmpc_handle* h, int32_t gp_id, int32_t M, const int32_t* idx_dev, const double* y_dev,
+                           double jitter, int32_t* ok_out, void* stream);
+
+/* The FITC mean gpmpc_gp_fitc installed for GP gp_id: *M (host, may be NULL) its inducing rows, 0 when none
+ * is installed; with idx_dev / w_dev non-NULL (device, int32 [M] / float64 [M]) the inducing indices and
+ * the weights are copied on `stream`. */
+gpmpc_status gpmpc_get_gp_fitc(gpmpc_handle* h, int32_t gp_id, int32_t* M, int32_t* idx_dev, double* w_dev,
+                               void* stream);
+
+/* Training rows of GP gp_id (inert rows included; with a FITC mean installed by gpmpc_gp_fitc still the
+ * training rows, not the inducing ones) and its capacity; either may be NULL. */
 gpmpc_status gpmpc_gp_size(gpmpc_handle* h, int32_t gp_id, int32_t* n, int32_t* capacity);
 
 /* Enable (1) / disable (0) the GP residual in the dynamics: 0 = nominal MPC
