@@ -133,6 +133,12 @@ struct FitcLayout {
 struct FitcOut {
     size_t m, rows = 0, tX = 4 * m, tW = 8 * m, idx = 12 * m, end = idx + m / 2;
 };
+// Scratch of gpmpc_gp_informative and gpmpc_gp_observe for b = max_batch points of a model with D = sum d_g GP inputs
+// and g GPs, in doubles: gathered inputs [b][D] | variances [g][b] | scores [b] | staged X_g [b][d_g], GP after GP |
+// staged y_g [g][b]
+struct ObserveLayout {
+    size_t b, D, g, zin = 0, var = b * D, score = var + g * b, sx = score + b, sy = sx + b * D, end = sy + g * b;
+};
 constexpr bool layouts_hold(size_t c) {
     return AppendLayout{c}.end == 16 * c + c + 256 + 16 + 1 && AppendLayout{c}.flag == 17 * c + 272 &&
            DropLayout{c}.end == 61 * c + 1 && DropLayout{c}.srows == 49 * c && RefactorLayout{c}.mask == 18 * c &&
@@ -183,6 +189,7 @@ struct gpmpc_handle {
     long long* stats = nullptr;            // optional per-instance solver statistics accumulators
     int32_t* scratch_i = nullptr;   // [2][max_batch]
     double* scratch_d = nullptr;    // [max_batch][4]
+    double* obs = nullptr;          // scratch of gpmpc_gp_informative / gpmpc_gp_observe (ObserveLayout), on first use
     // the batch whose tightening variances the last solve's variance launch wrote into `var`
     // (0: the last solve ran none, var is stale or unset)
     int var_batch = 0;
@@ -313,6 +320,7 @@ static void free_handle(gpmpc_handle* h) {
     if (h->cost) (void)hipFree(h->cost);
     if (h->scratch_i) (void)hipFree(h->scratch_i);
     if (h->scratch_d) (void)hipFree(h->scratch_d);
+    if (h->obs) (void)hipFree(h->obs);
     for (GPSlot& gs : h->gp) (void)gs.release(GPSlot::kBuffers);
     delete h;
 }
@@ -1834,6 +1842,180 @@ gpmpc_status gpmpc_plant_step(gpmpc_handle* h, int32_t batch, const double* para
         h->plant_params_valid = true;
     }
     HIPCHK(launch_plant(h->model, h->plant_params, h->P.dt, x, u, x_next, tstep, batch, s));
+    return GPMPC_OK;
+}
+
+// What is wrong with the transitions and picks of gpmpc_preprocess / gpmpc_gp_observe, or null
+static const char* transitions_bad(int32_t P, const double* x, const double* u, const double* xnext, int32_t m,
+                                   const int32_t* pick, double dt_diff, double gravity) {
+    if (P < 1 || m < 1) return "no transitions or no rows (P, m >= 1)";
+    if (!x || !u || !xnext) return "null transition array";
+    if (!pick && m > P) return "without picks the rows are transitions 0 .. m-1: m <= P";
+    if (!std::isfinite(dt_diff) || !(dt_diff > 0.0)) return "dt_diff must be finite and positive";
+    if (!std::isfinite(gravity)) return "gravity must be finite";
+    return nullptr;
+}
+
+static GPObserve observe_args(const gpmpc_handle* h, int32_t P, const double* x, const double* u, const double* xnext,
+                              int32_t m, const int32_t* pick, double dt_diff, double gravity) {
+    GPObserve a{};
+    a.model = h->model;
+    for (int i = 0; i < kMaxParams; ++i) a.params[i] = h->P.params[i];
+    a.P = P;
+    a.m = m;
+    a.x = x;
+    a.u = u;
+    a.xnext = xnext;
+    a.pick = pick;
+    a.dt_diff = dt_diff;
+    a.gravity = gravity;
+    return a;
+}
+
+static ObserveLayout observe_layout(const gpmpc_handle* h) {
+    size_t D = 0;
+    for (int g = 0; g < h->md.ngp; ++g) D += h->md.gp_dim[g];
+    return ObserveLayout{(size_t)h->max_batch, D, (size_t)h->md.ngp};
+}
+
+// The scratch of gpmpc_gp_informative / gpmpc_gp_observe, allocated by the first call that needs it (a setup step)
+static gpmpc_status ensure_observe_scratch(gpmpc_handle* h) {
+    if (h->obs) return GPMPC_OK;
+    const hipError_t e = hipMalloc(&h->obs, observe_layout(h).end * sizeof(double));
+    if (e != hipSuccess) {
+        h->obs = nullptr;
+        return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_preprocess(gpmpc_handle* h, int32_t P, const double* x_dev, const double* u_dev,
+                              const double* xnext_dev, int32_t m, const int32_t* pick_dev, double dt_diff,
+                              double gravity, double* inputs_dev, double* targets_dev, void* stream) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    const char* bad = transitions_bad(P, x_dev, u_dev, xnext_dev, m, pick_dev, dt_diff, gravity);
+    if (!bad && !inputs_dev && !targets_dev) bad = "no output (inputs_dev and targets_dev both NULL)";
+    if (bad) return fail(GPMPC_ERR_ARG, bad);
+    if (!h->model_set) return fail(GPMPC_ERR_STATE, "the prior parameters are not set (gpmpc_set_model first)");
+    (void)hipSetDevice(h->device);
+    GPObserve a = observe_args(h, P, x_dev, u_dev, xnext_dev, m, pick_dev, dt_diff, gravity);
+    a.inputs = inputs_dev;
+    a.targets = targets_dev;
+    HIPCHK(launch_gp_observe(a, (hipStream_t)stream));
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_informative(gpmpc_handle* h, int32_t P, const double* x_dev, const double* u_dev, int32_t m,
+                                  int32_t* pick_dev, double* score_dev, void* stream) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    if (P < 1 || P > h->max_batch) return fail(GPMPC_ERR_ARG, "P must be in 1 .. max_batch");
+    if (m < 1 || m > P) return fail(GPMPC_ERR_ARG, "m must be in 1 .. P");
+    if (!x_dev || !u_dev || !pick_dev) return fail(GPMPC_ERR_ARG, "null points or picks");
+    for (int g = 0; g < h->md.ngp; ++g) {
+        if (!h->gp[g].set) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
+        if (!h->gp[g].linvT) return fail(GPMPC_ERR_STATE, "the variance needs Linv (the GP was set without it)");
+    }
+    (void)hipSetDevice(h->device);
+    const gpmpc_status got = ensure_observe_scratch(h);
+    if (got != GPMPC_OK) return got;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const ObserveLayout lay = observe_layout(h);
+    // the GP inputs of the P points, as gpmpc_preprocess gathers them (no targets: x_next is not read)
+    GPObserve a = observe_args(h, P, x_dev, u_dev, nullptr, P, nullptr, 1.0, 0.0);
+    a.inputs = h->obs + lay.zin;
+    HIPCHK(launch_gp_observe(a, s));
+    GPRank r{};
+    r.Z = h->obs + lay.zin;
+    r.ldz = (int)lay.D;
+    r.var = h->obs + lay.var;
+    r.ldv = h->max_batch;
+    r.n_gp = h->md.ngp;
+    for (int g = 0, col = 0; g < h->md.ngp; col += h->md.gp_dim[g], ++g) {
+        // gpmpc_gp_predict's variance launch (with_noise = 0) on GP g's columns of the gathered rows
+        PostArgs pa{};
+        pa.Z = h->obs + lay.zin + col;
+        pa.ldz = (int)lay.D;
+        pa.P = P;
+        pa.d = h->md.gp_dim[g];
+        pa.with_noise = 0;
+        pa.var = h->obs + lay.var + (size_t)g * h->max_batch;
+        pa.var_stride = 1;
+        pa.var_off = 0;
+        HIPCHK(launch_gp_post(h->P.gp[g], h->gp[g].npad, pa, false, s, h->var_trim ? 0 : 1));
+        r.sf2[g] = h->P.gp[g].sf2;
+    }
+    r.P = P;
+    r.m = m;
+    r.score = h->obs + lay.score;
+    r.score_out = score_dev;
+    r.pick = pick_dev;
+    HIPCHK(launch_gp_score_rank(r, s));
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_observe(gpmpc_handle* h, int32_t P, const double* x_dev, const double* u_dev,
+                              const double* xnext_dev, int32_t m, const int32_t* pick_dev, double dt_diff,
+                              double gravity, int32_t evict_oldest, double* inputs_dev, double* targets_dev,
+                              int32_t* accepted_dev, int32_t* dropped_ok_dev, void* stream) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    const char* bad = transitions_bad(P, x_dev, u_dev, xnext_dev, m, pick_dev, dt_diff, gravity);
+    if (!bad && m > h->max_batch) bad = "more rows than max_batch (the staging scratch holds max_batch rows)";
+    if (bad) return fail(GPMPC_ERR_ARG, bad);
+    if (!h->model_set) return fail(GPMPC_ERR_STATE, "the prior parameters are not set (gpmpc_set_model first)");
+    // every refusal comes before any GP changes
+    const int ngp = h->md.ngp;
+    for (int g = 0; g < ngp; ++g) {
+        const gpmpc_status ready = gp_update_ready(h, g, kAppend, nullptr);
+        if (ready != GPMPC_OK) return ready;
+    }
+    const int n = h->P.gp[0].n, cap = h->gp[0].cap;
+    for (int g = 1; g < ngp; ++g)
+        if (h->P.gp[g].n != n || h->gp[g].cap != cap)
+            return fail(GPMPC_ERR_STATE, "the GPs differ in their training rows or capacity: the call appends the same rows to all");
+    const int64_t excess = (int64_t)n + m - cap;
+    if (excess > 0) {
+        if (!evict_oldest)
+            return fail(GPMPC_ERR_ARG, "capacity exceeded: " + std::to_string(n) + " + " + std::to_string(m) +
+                                           " rows, capacity " + std::to_string(cap) + " (gpmpc_gp_reserve, or evict_oldest)");
+        if (excess >= n)
+            return fail(GPMPC_ERR_ARG, "at least one row stays: " + std::to_string(excess) + " of " + std::to_string(n) +
+                                           " rows would be dropped");
+        for (int g = 0; g < ngp; ++g) {
+            const gpmpc_status ready = gp_update_ready(h, g, kDrop, nullptr);
+            if (ready != GPMPC_OK) return ready;
+        }
+    }
+    (void)hipSetDevice(h->device);
+    const gpmpc_status got = ensure_observe_scratch(h);
+    if (got != GPMPC_OK) return got;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const ObserveLayout lay = observe_layout(h);
+    GPObserve a = observe_args(h, P, x_dev, u_dev, xnext_dev, m, pick_dev, dt_diff, gravity);
+    a.inputs = inputs_dev;
+    a.targets = targets_dev;
+    for (int g = 0, col = 0; g < ngp; col += h->md.gp_dim[g], ++g) {
+        a.Xg[g] = h->obs + lay.sx + (size_t)h->max_batch * col;
+        a.yg[g] = h->obs + lay.sy + (size_t)h->max_batch * g;
+    }
+    HIPCHK(launch_gp_observe(a, s));
+    // the drops and appends are the calls a caller would make on the staged rows, GP after GP
+    const int ablk = (m + 15) / 16, dblk = excess > 0 ? (int)((excess + 15) / 16) : 1;
+    for (int g = 0; g < ngp; ++g) {
+        int32_t* dok = dropped_ok_dev ? dropped_ok_dev + (size_t)g * dblk : nullptr;
+        if (excess > 0) {
+            const gpmpc_status st = gpmpc_gp_drop_oldest(h, g, (int32_t)excess, dok, stream);
+            if (st != GPMPC_OK) return st;
+        } else if (dok) {
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)dok, 1, 1, s));
+        }
+        const gpmpc_status st = gpmpc_gp_append(h, g, m, a.Xg[g], a.yg[g],
+                                                accepted_dev ? accepted_dev + (size_t)g * ablk : nullptr, stream);
+        if (st != GPMPC_OK) return st;
+    }
     return GPMPC_OK;
 }
 

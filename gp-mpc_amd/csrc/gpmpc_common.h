@@ -444,8 +444,43 @@ struct GPFitc {
     int32_t* sidx;
 };
 
+// Transitions (x, u, x_next) turned into GP training rows (gp_observe.hip; gpmpc_preprocess, gpmpc_gp_informative
+// and gpmpc_gp_observe fill it): output row r comes from transition pick[r] (r when pick is null).  Every output may
+// be null; with targets, Xg and yg all null, xnext is not read (the inputs alone: gpmpc_gp_informative).
+struct GPObserve {
+    int32_t model;
+    double params[kMaxParams];   // the prior's (ProblemDev::params)
+    int32_t P, m;                // transitions, output rows
+    const double* x;             // [P][nx]
+    const double* u;             // [P][nu]
+    const double* xnext;         // [P][nx]
+    const int32_t* pick;         // [m] or null; an entry outside 0 .. P-1 reads nothing and gives a NaN row
+    double dt_diff, gravity;
+    double* inputs;              // [m][sum d_g]
+    double* targets;             // [m][n_gp]
+    double* Xg[kMaxGP];          // per GP [m][d_g]: the same values, contiguous (what gpmpc_gp_append reads)
+    double* yg[kMaxGP];          // per GP [m]
+};
+
 // Launchers (sqp_kernel.hip, gp_kernels.hip, gp_append.hip, gp_drop.hip, gp_refactor.hip, gp_fit.hip, gp_love.hip,
-// gp_fitc.hip; what the last six share, the tile pack's layout included, is in gp_tile.h).
+// gp_fitc.hip, gp_observe.hip; what the six before the last share, the tile pack's layout included, is in gp_tile.h).
+hipError_t launch_gp_observe(const GPObserve& a, hipStream_t stream);
+// score[i] = max_g var[g * ldv + i] / sf2[g] over n_gp GPs (a NaN among them gives NaN), and NaN for a point with a
+// non-finite GP input (the variance kernels' exponential is defined for finite arguments only: what they return for
+// such a point is unspecified); then pick[rank_i] = i for rank_i < m, rank_i the number of points that beat i: a
+// finite score beats a non-finite one, a larger finite one a smaller, and otherwise the lower index wins.
+struct GPRank {
+    const double* Z;      // [P][ldz] the points' gathered GP inputs
+    int32_t ldz;
+    const double* var;    // [n_gp][ldv]
+    int32_t ldv, n_gp;
+    double sf2[kMaxGP];
+    int32_t P, m;
+    double* score;        // [P] scratch
+    double* score_out;    // [P] the caller's copy, may be null
+    int32_t* pick;        // [m]
+};
+hipError_t launch_gp_score_rank(const GPRank& a, hipStream_t stream);
 hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream);
 hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream);
 hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream);

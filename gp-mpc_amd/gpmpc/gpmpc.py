@@ -321,6 +321,53 @@ class GPMPC:
 
         return self._update_gps(update)
 
+    def observe(self, x, u, x_next, pick=None, m: int | None = None, select: str | None = None,
+                evict_oldest: bool = False):
+        """``preprocess_data`` followed by ``append_data`` without leaving the device: transitions x (P, nx),
+        u (P, nu), x_next (P, nx) (device tensors as ``select_action_batch`` and ``plant_step`` produce them, or
+        host arrays) become GP training rows on the device and are appended to every GP of the solver handle
+        in one call (``BatchSolver.observe``, queued on the current stream).  The Python GP objects are extended
+        from the returned device tensors (``GaussianProcess.append_data`` / ``drop_oldest``), so they stay in
+        step without a host copy.
+
+        ``select=None``: the rows are the transitions ``pick`` names (int32 indices), or the first ``m`` (default
+        all).  ``select="variance"``: the ``m`` transitions where the GPs are least certain
+        (``BatchSolver.informative``; at most ``batch`` transitions).  ``evict_oldest``, the capacity check, the
+        LOVE roots, the device-built FITC means and the refusals in sparse mode are ``append_data``'s.  Returns
+        ``(inputs, targets, accepted, dropped_ok)`` as ``BatchSolver.observe`` does."""
+        if self.sparse and self.fitc != "device":
+            raise _lib.GPMPCError("observe: not available in sparse (FITC) mode")
+        assert self.gaussian_process is not None and not self._requires_recompile, \
+            "GP model must be uploaded (call reset())"
+        if select not in (None, "variance"):
+            raise ValueError("select must be None or 'variance'")
+        s = self.solver
+        x, u, x_next = s._transitions(x, u, x_next)
+        if select == "variance":
+            if pick is not None or m is None:
+                raise ValueError("select='variance' chooses the rows itself: pass m, not pick")
+            rows = int(m)
+        else:
+            pick, rows = s._picks(pick, m, x.shape[0])
+        n, cap = s.gp_size(0)
+        excess = n + rows - cap
+        # before any GP changes, so the handle's GPs stay in step (an eviction leaves at least one old row)
+        if excess > 0 and (not evict_oldest or excess >= n):
+            raise _lib.GPMPCError(f"observe: capacity exceeded ({n} + {rows} rows, capacity {cap}; "
+                                  "construct GPMPC with gp_capacity)")
+
+        def update():
+            p = s.informative(x, u, rows) if select == "variance" else pick
+            out = s.observe(x, u, x_next, pick=p, m=rows, evict_oldest=evict_oldest)
+            inputs, targets = out[0], out[1]
+            for i, idx in enumerate(self.gp_idx):
+                if excess > 0:
+                    self.gaussian_process[i].drop_oldest(excess)
+                self.gaussian_process[i].append_data(inputs[:, idx], targets[:, i])
+            return out
+
+        return self._update_gps(update)
+
     def refresh_gps(self, hyperparameters: list | None = None) -> list[torch.Tensor]:
         """Factorise every GP on the solver handle again from scratch, on the device
         (``BatchSolver.refactor_gp``, queued on the current stream, no upload): from the handle's own

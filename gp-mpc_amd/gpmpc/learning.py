@@ -7,7 +7,8 @@ parameters), so B episodes run at once on the GPU; transitions are gathered from
 
 * :func:`run_evaluation` -- one closed-loop episode per instance (`run_gp_mpc.py:42-72`)
 * :func:`run_online_episode` -- the same episode, learning while it runs: a few of every step's
-  transitions are appended to the uploaded GPs on the device (``GPMPC.append_data``); no
+  transitions are appended to the uploaded GPs on the device (``GPMPC.append_data``, or with
+  ``device_data=True`` ``GPMPC.observe``, which preprocesses them on the device too); no
   counterpart in the reference, whose loop is episodic
 * :func:`sample_data`    -- random transitions of an episode batch (`run_gp_mpc.py:75-83`)
 * :func:`learn`          -- prior run, then per epoch: sample, ``preprocess_data``,
@@ -59,7 +60,8 @@ def run_evaluation(ctrl, x0: np.ndarray, steps: int, tstep0: np.ndarray | None =
 
 
 def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, seed: int,
-                       tstep0: np.ndarray | None = None, sliding: bool = False, refresh_every: int = 0) -> dict:
+                       tstep0: np.ndarray | None = None, sliding: bool = False, refresh_every: int = 0,
+                       device_data: bool = False, select: str = "random") -> dict:
     """A closed-loop episode that learns while it runs: after every plant step a seeded random
     choice of ``append_per_step`` of the step's B transitions is preprocessed
     (``GPMPC.preprocess_data``) and appended to the uploaded GPs (``GPMPC.append_data``, a
@@ -70,8 +72,22 @@ def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, s
     ``append_per_step`` rows, the oldest rows making room for them on the device
     (``append_data(evict_oldest=True)``), so the training set is a moving window of fixed size.
 
+    ``device_data=True`` keeps the data where it is born: ``obs``, ``action`` and ``status`` live in
+    preallocated device tensors that are copied out once at the end, and learning goes through
+    ``GPMPC.observe`` (preprocessing and append on the device).  The host generator still draws the random
+    picks, with the same call and seed as the host path, so both paths learn from the same transitions;
+    the only upload per step is those picks, an int32 index tensor.  ``select="variance"`` (needs
+    ``device_data=True``) picks the step's transitions where the GPs are least certain instead
+    (``BatchSolver.informative``) and uploads nothing.  The two paths differ by rounding in the targets.
+
     Returns the dict of :func:`run_evaluation` plus ``n_train`` (steps,), the training rows after
-    each step."""
+    each step; with ``device_data=True`` also ``pick``, the list of every step's picked indices."""
+    if select not in ("random", "variance"):
+        raise ValueError("select must be 'random' or 'variance'")
+    if select == "variance" and not device_data:
+        raise ValueError("select='variance' picks on the device: it needs device_data=True")
+    if device_data:
+        return _run_online_episode_device(ctrl, x0, steps, append_per_step, seed, tstep0, sliding, refresh_every, select)
     ctrl.reset()
     solver = ctrl.solver
     dev = solver.device
@@ -102,6 +118,54 @@ def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, s
             ctrl.refresh_gps()
         data["n_train"].append(solver.gp_size(0)[0])
     return {k: np.array(v) for k, v in data.items()}
+
+
+def _run_online_episode_device(ctrl, x0, steps, append_per_step, seed, tstep0, sliding, refresh_every, select) -> dict:
+    """:func:`run_online_episode` with ``device_data=True``: the same loop on device tensors."""
+    ctrl.reset()
+    solver = ctrl.solver
+    dev = solver.device
+    B = solver.batch
+    rng = np.random.default_rng(seed)
+    obs = torch.empty(steps + 1, B, solver.nx, dtype=torch.float64, device=dev)
+    action = torch.empty(steps, B, solver.nu, dtype=torch.float64, device=dev)
+    status = torch.empty(steps, B, dtype=torch.int32, device=dev)
+    obs[0].copy_(torch.as_tensor(np.asarray(x0, dtype=np.float64).reshape(B, -1)))
+    ts = torch.tensor(np.zeros(B) if tstep0 is None else tstep0, dtype=torch.int32, device=dev)
+    times, n_train, picks = [], [], []
+    for step in range(steps):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        u = ctrl.select_action_batch(obs[step], ts.clone())
+        torch.cuda.synchronize(dev)
+        times.append(time.perf_counter() - t0)
+        action[step].copy_(u)
+        status[step].copy_(solver.status)
+        solver.plant_step(obs[step], action[step], ts, out=obs[step + 1])   # advances the reference index too
+        n, cap = solver.gp_size(0)
+        room = None if sliding else max(cap - n, 0)
+        if select == "random":
+            pick = rng.choice(B, min(append_per_step, B), replace=False)
+            if not sliding:
+                pick = pick[:room]
+            if len(pick):
+                pick = torch.as_tensor(pick.astype(np.int32)).to(dev)
+                ctrl.observe(obs[step], action[step], obs[step + 1], pick=pick, evict_oldest=sliding)
+            picks.append(pick)
+        else:
+            m = min(append_per_step, B) if sliding else min(append_per_step, B, room)
+            pick = np.zeros(0, dtype=np.int32)
+            if m:
+                # (the indices are read back after the episode; the rows they name are the appended inputs)
+                pick = solver.informative(obs[step], action[step], m)
+                ctrl.observe(obs[step], action[step], obs[step + 1], pick=pick, evict_oldest=sliding)
+            picks.append(pick)
+        if refresh_every > 0 and (step + 1) % refresh_every == 0:
+            ctrl.refresh_gps()
+        n_train.append(solver.gp_size(0)[0])
+    return {"obs": obs.cpu().numpy(), "action": action.cpu().numpy(), "status": status.cpu().numpy(),
+            "inference_time_data": np.array(times), "n_train": np.array(n_train),
+            "pick": [p.cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p, dtype=np.int32) for p in picks]}
 
 
 def sample_data(data: dict, n_samples: int, rng: np.random.Generator):

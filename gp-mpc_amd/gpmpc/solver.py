@@ -208,6 +208,93 @@ class BatchSolver:
         _lib.check(self.lib.gpmpc_gp_drop_oldest(self._h, int(gp_id), m, flags.data_ptr(), self._stream()))
         return flags
 
+    # ------------------------------------------------------------------ training data on the device
+    def _diff_constants(self) -> tuple[float, float]:
+        """(dt_diff, gravity) of ``GPMPC.preprocess_data``: the reference's literals 1/60 and 9.81 for quad3d
+        (`gpmpc/gpmpc.py:113-151`), the model's own dt and gravity otherwise."""
+        return (1 / 60, 9.81) if self.spec.name == "quad3d" else (self.spec.dt, self.spec.gravity)
+
+    def _transitions(self, x, u, x_next=None):
+        """x (P, nx), u (P, nu) and x_next (P, nx) as contiguous float64 device tensors."""
+        x = torch.as_tensor(x).to(self.device, torch.float64).reshape(-1, self.nx).contiguous()
+        u = torch.as_tensor(u).to(self.device, torch.float64).reshape(-1, self.nu).contiguous()
+        if u.shape[0] != x.shape[0]:
+            raise ValueError("x and u disagree on the number of transitions")
+        if x_next is None:
+            return x, u
+        x_next = torch.as_tensor(x_next).to(self.device, torch.float64).reshape(-1, self.nx).contiguous()
+        if x_next.shape[0] != x.shape[0]:
+            raise ValueError("x and x_next disagree on the number of transitions")
+        return x, u, x_next
+
+    def _picks(self, pick, m, P):
+        """(pick as an int32 device tensor or None, rows m): ``pick`` given, its length is m; else rows 0 .. m-1
+        (all P by default)."""
+        if pick is None:
+            return None, int(P if m is None else m)
+        pick = torch.as_tensor(pick).to(self.device, torch.int32).reshape(-1).contiguous()
+        if m is not None and int(m) != pick.shape[0]:
+            raise ValueError(f"pick holds {pick.shape[0]} indices, m is {m}")
+        return pick, int(pick.shape[0])
+
+    def preprocess(self, x, u, x_next, pick=None, m=None):
+        """GP training inputs (m, sum d_g) and targets (m, n_gp) from transitions x (P, nx), u (P, nu),
+        x_next (P, nx), on the current stream (gpmpc_preprocess): ``GPMPC.preprocess_data`` on the device, at the
+        handle's prior parameters.  Row r comes from transition ``pick[r]`` (int32 indices; an index outside
+        0 .. P-1 gives a row of NaN), or from transition r of the first ``m`` (default all) without ``pick``.
+        cuda or host tensors (or arrays); no synchronisation of its own.  Returns device tensors."""
+        x, u, x_next = self._transitions(x, u, x_next)
+        pick, m = self._picks(pick, m, x.shape[0])
+        inputs = torch.empty(max(m, 0), sum(self.spec.gp_dims), dtype=torch.float64, device=self.device)
+        targets = torch.empty(max(m, 0), self.spec.n_gp, dtype=torch.float64, device=self.device)
+        dt_diff, gravity = self._diff_constants()
+        _lib.check(self.lib.gpmpc_preprocess(self._h, x.shape[0], x.data_ptr(), u.data_ptr(), x_next.data_ptr(), m,
+                                             _lib.ptr(pick), dt_diff, gravity, inputs.data_ptr(), targets.data_ptr(),
+                                             self._stream()))
+        return inputs, targets
+
+    def informative(self, x, u, m: int, scores: bool = False):
+        """The ``m`` of the P <= batch points (x (P, nx), u (P, nu)) where the handle's GPs are least certain
+        (gpmpc_gp_informative): a device int32 tensor (m,) of indices by decreasing score, the score being the
+        largest exact posterior variance over the GPs, each divided by its outputscale (no likelihood noise; LOVE
+        roots and FITC means are ignored).  Ties go to the lower index, a non-finite score ranks last.  The picks
+        are the most uncertain points one by one; redundancy among them is not accounted for.  On the current
+        stream, no synchronisation of its own.  ``scores=True`` also returns the (P,) scores."""
+        x, u = self._transitions(x, u)
+        P = x.shape[0]
+        pick = torch.empty(max(int(m), 0), dtype=torch.int32, device=self.device)
+        score = torch.empty(P, dtype=torch.float64, device=self.device) if scores else None
+        _lib.check(self.lib.gpmpc_gp_informative(self._h, P, x.data_ptr(), u.data_ptr(), int(m), pick.data_ptr(),
+                                                 _lib.ptr(score), self._stream()))
+        return (pick, score) if scores else pick
+
+    def observe(self, x, u, x_next, pick=None, m=None, evict_oldest: bool = False):
+        """``preprocess`` followed by an append of the m rows to every GP of the handle, in one call on the
+        current stream (gpmpc_gp_observe; m <= batch): bit-identical to ``preprocess``, a column slice per GP,
+        ``drop_gp`` where needed and ``append_gp``.  With ``evict_oldest`` and n + m above the capacity exactly
+        the excess is dropped from the old end of every GP first.  Returns ``(inputs, targets, accepted,
+        dropped_ok)``: the rows as ``preprocess`` returns them (the caller keeps the targets) and the int32 flags
+        (n_gp, blocks) of ``append_gp`` and ``drop_gp`` (1 where nothing was dropped).  No synchronisation of its
+        own.  The Python GP objects are not touched."""
+        x, u, x_next = self._transitions(x, u, x_next)
+        pick, m = self._picks(pick, m, x.shape[0])
+        n_gp = self.spec.n_gp
+        try:
+            n, cap = self.gp_size(0)
+        except _lib.GPMPCError:   # (an unset GP is the library's refusal below, like every other precondition)
+            n, cap = 0, 0
+        excess = max(n + m - cap, 0) if evict_oldest else 0
+        inputs = torch.empty(max(m, 0), sum(self.spec.gp_dims), dtype=torch.float64, device=self.device)
+        targets = torch.empty(max(m, 0), n_gp, dtype=torch.float64, device=self.device)
+        accepted = torch.empty(n_gp, max((m + 15) // 16, 1), dtype=torch.int32, device=self.device)
+        dropped_ok = torch.empty(n_gp, max((excess + 15) // 16, 1), dtype=torch.int32, device=self.device)
+        dt_diff, gravity = self._diff_constants()
+        _lib.check(self.lib.gpmpc_gp_observe(self._h, x.shape[0], x.data_ptr(), u.data_ptr(), x_next.data_ptr(), m,
+                                             _lib.ptr(pick), dt_diff, gravity, int(bool(evict_oldest)),
+                                             inputs.data_ptr(), targets.data_ptr(), accepted.data_ptr(),
+                                             dropped_ok.data_ptr(), self._stream()))
+        return inputs, targets, accepted, dropped_ok
+
     def refactor_gp(self, gp_id: int, y, lengthscale: float, outputscale: float, noise: float) -> torch.Tensor:
         """Factorise the handle's GP ``gp_id`` again from scratch on the current stream
         (gpmpc_gp_refactor): from the handle's own training inputs, the targets ``y`` (n,) of its n

@@ -359,6 +359,67 @@ gpmpc_status gpmpc_gp_posterior(int32_t n, int32_t d, int32_t npad, const double
 gpmpc_status gpmpc_plant_step(gpmpc_handle* h, int32_t batch, const double* params, const double* x,
                               const double* u, double* x_next, int32_t* tstep, void* stream);
 
+/* GP training rows from transitions, on the device: GPMPC.preprocess_data of the build (the reference's
+ * gpmpc/gpmpc.py:113-151) for the handle's model, csrc/gp_observe.hip.  x_dev [P][nx], u_dev [P][nu] and
+ * xnext_dev [P][nx] are P transitions; output row r comes from transition pick_dev[r], r = 0 .. m-1 (pick_dev
+ * NULL: from transition r, and then m <= P).  inputs_dev [m][sum d_g] and targets_dev [m][n_gp], row-major, have
+ * the shapes and the column order preprocess_data returns; either may be NULL, not both.  The inputs are copies of
+ * z[gp_src_g], z = [x; u].  The targets start from x_dot = (x_next - x) / dt_diff: for quad2d and quad3d the thrust
+ * target is sqrt(sum of the squared velocity components of x_dot, `gravity` added to the z-component) minus
+ * (a u_0 + b), and the rate targets are x_dot_j - f_j(x, u); cartpole's two targets are its two acceleration
+ * residuals.  f is the prior dynamics (csrc/models.h, zero GP means) at the parameters gpmpc_set_model was given,
+ * not the plant's.  dt_diff and gravity are the caller's: the reference's literals 1/60 and 9.81 for quad3d, the
+ * model's dt and gravity otherwise.
+ * One kernel launch on `stream`, no host synchronisation, nothing of the handle changes.  A pick outside 0 .. P-1
+ * reads nothing and gives a row of NaN; a non-finite transition propagates as NaN or Inf, nothing is refused on
+ * the device.
+ * Refused: P < 1, m < 1, a NULL transition array, both outputs NULL, pick_dev NULL with m > P, dt_diff not finite
+ * and positive, gravity not finite (GPMPC_ERR_ARG); a call before gpmpc_set_model (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_preprocess(gpmpc_handle* h, int32_t P, const double* x_dev, const double* u_dev,
+                              const double* xnext_dev, int32_t m, const int32_t* pick_dev, double dt_diff,
+                              double gravity, double* inputs_dev, double* targets_dev, void* stream);
+
+/* The m of P points z_i = [x_i; u_i] (device, x_dev [P][nx], u_dev [P][nu]) where the GPs are least certain:
+ * score s_i = max over the GPs g of var_g(z_i[gp_src_g]) / outputscale_g, var_g the exact posterior variance
+ * without likelihood noise over GP g's training rows.  The inputs are gathered as gpmpc_preprocess gathers them
+ * and the variance is the launch behind gpmpc_gp_predict(with_noise = 0), so the scores are bit-identical to that
+ * call on those inputs, divided by the outputscale; a LOVE root and a FITC mean are ignored, as gpmpc_gp_predict
+ * ignores them.  A NaN among a point's variances makes its score NaN, and so does a non-finite value among its GP
+ * inputs (what the variance launch returns for such a point is unspecified).
+ * pick_dev (device int32 [m]) receives the indices of the m largest scores in decreasing order; ties go to the
+ * lower index, and a score that is not finite ranks after every finite one, again lower index first.  The rank
+ * is counted (rank_i = the number of points that beat i, O(P^2) comparisons), so every output is fixed bit for
+ * bit.  score_dev (device float64 [P]) receives the scores, may be NULL.  The picks are the m most uncertain
+ * points one by one: no account is taken of redundancy among them, and near-duplicates may all be picked.
+ * Asynchronous on `stream`, no host synchronisation; the first call allocates the handle's scratch for max_batch
+ * points, a synchronous setup step like gpmpc_gp_reserve.
+ * Refused: P < 1, P > max_batch, m < 1, m > P, NULL x_dev, u_dev or pick_dev (GPMPC_ERR_ARG); a GP of the model
+ * not set, or set without Linv (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_gp_informative(gpmpc_handle* h, int32_t P, const double* x_dev, const double* u_dev, int32_t m,
+                                  int32_t* pick_dev, double* score_dev, void* stream);
+
+/* gpmpc_preprocess followed by an append of the m rows to every GP of the handle, in one stream-ordered call:
+ * the rows are staged per GP (X_g [m][d_g], y_g [m]) in scratch of the handle, which holds max_batch rows and is
+ * allocated on first use (a synchronous setup step), and appended by gpmpc_gp_append's own launches.  With
+ * evict_oldest = 1 and n + m above the capacity, exactly the excess is dropped first from every GP by
+ * gpmpc_gp_drop_oldest's launches; at least one old row stays.  Afterwards the GPs are bit-identical to
+ * gpmpc_preprocess, a slice of its outputs' columns per GP, gpmpc_gp_drop_oldest where needed and
+ * gpmpc_gp_append, GP after GP, on the same handle state.  inputs_dev and targets_dev as for gpmpc_preprocess,
+ * here both may be NULL: they are copies for the caller, who keeps the targets (the handle stores none).
+ * accepted_dev: device int32 [n_gp][ceil(m/16)], per GP as gpmpc_gp_append reports; dropped_ok_dev: device int32
+ * [n_gp][max(ceil(excess/16), 1)], per GP as gpmpc_gp_drop_oldest reports, 1 where nothing was dropped; both may
+ * be NULL.  A row of NaN (a pick out of range, a non-finite transition) makes its block inert and reports 0, as
+ * gpmpc_gp_append defines it.  No host synchronisation.
+ * Refused before any GP changes: what gpmpc_preprocess refuses of its transitions, picks, dt_diff and gravity,
+ * m > max_batch, n + m above the capacity without evict_oldest, an excess >= n with it (GPMPC_ERR_ARG); a call
+ * before gpmpc_set_model, what gpmpc_gp_append refuses of any GP of the model -- not set, set without Linv, a FITC
+ * upload, a LOVE root or a FITC mean installed --, where rows must be dropped no gpmpc_gp_reserve, and GPs that
+ * differ in their row count or capacity (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_gp_observe(gpmpc_handle* h, int32_t P, const double* x_dev, const double* u_dev,
+                              const double* xnext_dev, int32_t m, const int32_t* pick_dev, double dt_diff,
+                              double gravity, int32_t evict_oldest, double* inputs_dev, double* targets_dev,
+                              int32_t* accepted_dev, int32_t* dropped_ok_dev, void* stream);
+
 /* Launch shape of the SQP kernel (no reference counterpart: the reference solves one instance).
  *   waves     0 = auto: one wavefront per instance, or -- for the models whose stage fits one MFMA
  *             tile (quad2d, cartpole) -- four per instance when batch <= the device's compute units
