@@ -12,6 +12,13 @@ recursion as a convolution, in another order); instance 1's row must be exactly 
 Shapes: odd and even term counts, H = 1 (one term), H + 1 = 32 (the half-wave boundary: H = 31
 is the largest split horizon), every (NUNC, NB): quad2d (3, 8), cartpole (2, 5: an odd NB, unequal
 halves), quad3d (its table does not fit in LDS: the global-memory loop).
+
+Above the split layout (H >= 32: one lane per stage, every variable of a stage in its lane): H = 32
+(quad2d's table of H NB NUNC = 768 entries fills the first pass of the staging loop exactly),
+H = 33 and 48 (the loop's second pass, "the rest of the table"; for cartpole the table stays
+within one pass up to H = 63), H = 63 (all 64 lanes) and quad3d at its longest horizon, H = 47.
+With the second pass's store removed the quad2d cases at H >= 33 fail and every shorter one passes
+(profiles/r17/README.md).
 """
 
 import numpy as np
@@ -22,7 +29,9 @@ from helpers import O, initial_states, lqr, oracle_gps, problem, product_gps
 pytestmark = pytest.mark.gpu
 
 CASES = [("quad2d", 30, 1), ("quad2d", 30, 2), ("quad2d", 30, 5), ("quad2d", 40, 30), ("quad2d", 40, 31),
-         ("cartpole", 20, 2), ("cartpole", 30, 11), ("cartpole", 30, 20), ("quad3d", 24, 8)]
+         ("cartpole", 20, 2), ("cartpole", 30, 11), ("cartpole", 30, 20), ("quad3d", 24, 8),
+         ("quad2d", 40, 32), ("quad2d", 40, 33), ("quad2d", 40, 48), ("quad2d", 40, 63),
+         ("cartpole", 30, 32), ("cartpole", 30, 63), ("quad3d", 24, 47)]
 
 
 @pytest.mark.parametrize("name,N,H", CASES)
