@@ -139,6 +139,28 @@ struct FitcOut {
 struct ObserveLayout {
     size_t b, D, g, zin = 0, var = b * D, score = var + g * b, sx = score + b, sy = sx + b * D, end = sy + g * b;
 };
+// Scratch of gpmpc_gp_select for max_batch = b candidates (stride ldp: b rounded up to the pick loop's block) and GPs
+// of c_g padded rows, in doubles: V_g^T [c_g][ldp], GP after GP | the l columns [g][256][ldp] | d [2][g][ldp] | the
+// blocks' best scores [2][nblk] | their indices [2][nblk][2] int32 | the candidates' state [ldp] int32
+struct SelectLayout {
+    size_t ldp, nblk, g, vt[kMaxGP], lcol, d, bval, bidx, state, end;
+    SelectLayout(size_t b, size_t ngp, const size_t* rows) {
+        ldp = (b + kSelectBlock - 1) / kSelectBlock * kSelectBlock;
+        nblk = ldp / kSelectBlock;
+        g = ngp;
+        size_t at = 0;
+        for (size_t q = 0; q < (size_t)kMaxGP; ++q) {
+            vt[q] = at;
+            if (q < ngp) at += rows[q] * ldp;
+        }
+        lcol = at;
+        d = lcol + ngp * kSelectMaxPicks * ldp;
+        bval = d + 2 * ngp * ldp;
+        bidx = bval + 2 * nblk;
+        state = bidx + 2 * nblk;
+        end = state + ldp / 2;
+    }
+};
 constexpr bool layouts_hold(size_t c) {
     return AppendLayout{c}.end == 16 * c + c + 256 + 16 + 1 && AppendLayout{c}.flag == 17 * c + 272 &&
            DropLayout{c}.end == 61 * c + 1 && DropLayout{c}.srows == 49 * c && RefactorLayout{c}.mask == 18 * c &&
@@ -190,6 +212,8 @@ struct gpmpc_handle {
     int32_t* scratch_i = nullptr;   // [2][max_batch]
     double* scratch_d = nullptr;    // [max_batch][4]
     double* obs = nullptr;          // scratch of gpmpc_gp_informative / gpmpc_gp_observe (ObserveLayout), on first use
+    double* sel = nullptr;          // scratch of gpmpc_gp_select (SelectLayout), on first use and when a capacity has grown
+    size_t sel_rows[kMaxGP] = {0, 0, 0, 0};   // the padded rows its V regions were sized for
     // the batch whose tightening variances the last solve's variance launch wrote into `var`
     // (0: the last solve ran none, var is stale or unset)
     int var_batch = 0;
@@ -321,6 +345,7 @@ static void free_handle(gpmpc_handle* h) {
     if (h->scratch_i) (void)hipFree(h->scratch_i);
     if (h->scratch_d) (void)hipFree(h->scratch_d);
     if (h->obs) (void)hipFree(h->obs);
+    if (h->sel) (void)hipFree(h->sel);
     for (GPSlot& gs : h->gp) (void)gs.release(GPSlot::kBuffers);
     delete h;
 }
@@ -1952,6 +1977,97 @@ gpmpc_status gpmpc_gp_informative(gpmpc_handle* h, int32_t P, const double* x_de
     r.score_out = score_dev;
     r.pick = pick_dev;
     HIPCHK(launch_gp_score_rank(r, s));
+    return GPMPC_OK;
+}
+
+// The scratch of gpmpc_gp_select: made by the first call and made again when a GP's capacity has grown past what its
+// V region holds (a synchronous setup step).  A failed allocation leaves the handle as it was.
+static gpmpc_status ensure_select_scratch(gpmpc_handle* h) {
+    size_t rows[kMaxGP] = {0, 0, 0, 0};
+    bool fits = h->sel != nullptr;
+    for (int g = 0; g < h->md.ngp; ++g) {
+        rows[g] = (size_t)std::max((h->gp[g].cap + 15) / 16 * 16, h->gp[g].npad);
+        fits = fits && rows[g] <= h->sel_rows[g];
+    }
+    if (fits) return GPMPC_OK;
+    double* fresh = nullptr;
+    const hipError_t e = hipMalloc(&fresh, SelectLayout((size_t)h->max_batch, (size_t)h->md.ngp, rows).end * sizeof(double));
+    if (e != hipSuccess) return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    if (h->sel) (void)hipFree(h->sel);   // (waits for the work queued on it)
+    h->sel = fresh;
+    for (int g = 0; g < kMaxGP; ++g) h->sel_rows[g] = rows[g];
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_select(gpmpc_handle* h, int32_t P, const double* x_dev, const double* u_dev, int32_t m,
+                             int32_t* pick_dev, double* gain_dev, double* resid_dev, int32_t* ok_dev, void* stream) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    if (P < 1 || P > h->max_batch) return fail(GPMPC_ERR_ARG, "P must be in 1 .. max_batch");
+    if (m < 1 || m > P) return fail(GPMPC_ERR_ARG, "m must be in 1 .. P");
+    if (m > kSelectMaxPicks) return fail(GPMPC_ERR_ARG, "m must be at most " + std::to_string(kSelectMaxPicks));
+    if (!x_dev || !u_dev || !pick_dev) return fail(GPMPC_ERR_ARG, "null points or picks");
+    for (int g = 0; g < h->md.ngp; ++g) {
+        if (!h->gp[g].set) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
+        if (!h->gp[g].linvT) return fail(GPMPC_ERR_STATE, "the variance needs Linv (the GP was set without it)");
+    }
+    (void)hipSetDevice(h->device);
+    gpmpc_status got = ensure_observe_scratch(h);
+    if (got != GPMPC_OK) return got;
+    got = ensure_select_scratch(h);
+    if (got != GPMPC_OK) return got;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const ObserveLayout lay = observe_layout(h);
+    const SelectLayout sl((size_t)h->max_batch, (size_t)h->md.ngp, h->sel_rows);
+    // the GP inputs of the P candidates and their start variances: gpmpc_gp_informative's launches
+    GPObserve a = observe_args(h, P, x_dev, u_dev, nullptr, P, nullptr, 1.0, 0.0);
+    a.inputs = h->obs + lay.zin;
+    HIPCHK(launch_gp_observe(a, s));
+    GPSelect q{};
+    q.P = P;
+    q.m = m;
+    q.n_gp = h->md.ngp;
+    q.ldp = (int)sl.ldp;
+    q.nblk = (P + kSelectBlock - 1) / kSelectBlock;
+    q.Z = h->obs + lay.zin;
+    q.ldz = (int)lay.D;
+    q.var0 = h->obs + lay.var;
+    q.ldv = h->max_batch;
+    for (int g = 0, col = 0; g < h->md.ngp; col += h->md.gp_dim[g], ++g) {
+        PostArgs pa{};
+        pa.Z = h->obs + lay.zin + col;
+        pa.ldz = (int)lay.D;
+        pa.P = P;
+        pa.d = h->md.gp_dim[g];
+        pa.with_noise = 0;
+        pa.var = h->obs + lay.var + (size_t)g * h->max_batch;
+        pa.var_stride = 1;
+        pa.var_off = 0;
+        HIPCHK(launch_gp_post(h->P.gp[g], h->gp[g].npad, pa, false, s, h->var_trim ? 0 : 1));
+        const GPDev& gd = h->P.gp[g];
+        GPSelectGP& sg = q.g[g];
+        sg.rows = gd.vrows;
+        sg.linvT = gd.linvT;
+        sg.Vt = h->sel + sl.vt[g];
+        sg.lcol = h->sel + sl.lcol + (size_t)g * kSelectMaxPicks * sl.ldp;
+        sg.npad = h->gp[g].npad;
+        sg.nv = gd.nv;
+        sg.d = h->md.gp_dim[g];
+        sg.zcol = col;
+        sg.c = -0.5 * gd.inv_ell2;
+        sg.sf2 = gd.sf2;
+        sg.sn2 = gd.sn2;
+    }
+    q.d = h->sel + sl.d;
+    q.bval = h->sel + sl.bval;
+    q.bidx = reinterpret_cast<int32_t*>(h->sel + sl.bidx);
+    q.state = reinterpret_cast<int32_t*>(h->sel + sl.state);
+    q.pick = pick_dev;
+    q.gain = gain_dev;
+    q.resid = resid_dev;
+    q.ok = ok_dev;
+    HIPCHK(launch_gp_select(q, s));
     return GPMPC_OK;
 }
 

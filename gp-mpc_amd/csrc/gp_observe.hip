@@ -1,6 +1,8 @@
 // GP training rows from transitions on the device (gpmpc_preprocess, gpmpc_gp_informative, gpmpc_gp_observe): the
 // device restatement of GPMPC.preprocess_data (gpmpc/gpmpc.py, the reference's gpmpc/gpmpc.py:113-151) and the
 // counting rank of the points' variance scores.  One thread per output row; nothing here synchronises the host.
+// Below them the greedy conditional-variance selection (gpmpc_gp_select): the V kernel and the pick loop.
+#include "gp_tile.h"
 #include "gpmpc_common.h"
 #include "models.h"
 
@@ -112,7 +114,291 @@ __global__ void gp_rank_kernel(const GPRank a) {
     if (rank < a.m) a.pick[rank] = i;
 }
 
+// ---------------------------------------------------------------------------- greedy selection (gpmpc_gp_select)
+// V_g = K_ZX L_g^-T for the P candidates and every GP of the model (grid.y), contracted as gp_post_kernel contracts
+// it: one wave = 16 candidates, the A operand's kernel values generated on the fly (one exp per lane per K-step), the
+// 16-row panels of (L^-1)^T staged in LDS for the workgroup's four waves, only the upper triangle loaded and
+// multiplied, column groups of kSelCT tiles looped for npad > 256.  The accumulator tiles are stored, transposed:
+// Vt[column][candidate], the layout the pick loop reads coalesced over its candidates.
+constexpr int kSelWaves = 4;
+constexpr int kSelCT = 16;
+constexpr int kSelStride = 16 * (kSelCT | 1);   // odd number of tiles per LDS row, as gp_post_kernel's
+
+// k_g(z, z') of two gathered candidates, the operations of the variance kernels' kernel value
+__device__ __forceinline__ double select_kernel_value(const GPSelectGP& g, const double* zi, const double* zj) {
+    double q = 0.0;
+#pragma unroll
+    for (int dd = 0; dd < 3; ++dd) {
+        const int k = dd < g.d ? dd : 0;   // (nothing is read past the GP's own columns)
+        const double df = (dd < g.d) ? zj[k] - zi[k] : 0.0;
+        q = fma(df, df, q);
+    }
+    return g.sf2 * exp_rbf(g.c * q);
+}
+
+__global__ __launch_bounds__(64 * kSelWaves) void gp_select_v_kernel(const GPSelect a) {
+    __shared__ __attribute__((aligned(16))) double panel[16 * kSelStride];
+    const GPSelectGP g = a.g[blockIdx.y];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int lc = lane & 15, kq = lane >> 4;
+    const int p0 = (blockIdx.x * kSelWaves + wave) * 16;
+    const int p = min(p0 + lc, a.P - 1);   // (a lane past the end repeats the last candidate and stores nothing)
+    double z[3];
+#pragma unroll
+    for (int dd = 0; dd < 3; ++dd) z[dd] = (dd < g.d) ? a.Z[(size_t)p * a.ldz + g.zcol + dd] : 0.0;
+    const double4* rows = reinterpret_cast<const double4*>(g.rows);
+    const int ntile = g.npad / 16;
+    for (int t0 = 0; t0 < ntile; t0 += kSelCT) {
+        const int tn = min(kSelCT, ntile - t0);
+        const int npan = t0 + tn;   // K rows below 16 (t0 + tn): the upper triangle
+        f64x4 acc[kSelCT];
+#pragma unroll
+        for (int t = 0; t < kSelCT; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+        for (int pan = 0; pan < npan; ++pan) {
+            const int lt0 = max(pan - t0, 0), w = 16 * (tn - lt0);
+            __syncthreads();   // the previous panel has been read
+            for (int e = tid; e < 16 * w; e += 64 * kSelWaves) {
+                const int row = e / w, col = e - row * w;
+                panel[row * kSelStride + 16 * lt0 + col] = g.linvT[(size_t)(16 * pan + row) * g.npad + 16 * (t0 + lt0) + col];
+            }
+            double kv[4];
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const int i = 16 * pan + 4 * ks + kq;
+                const double4 r = rows[i < g.nv ? i : 0];
+                const double xr[3] = {r.x, r.y, r.z};
+                double q = 0.0;
+#pragma unroll
+                for (int dd = 0; dd < 3; ++dd) {
+                    const double df = (dd < g.d) ? xr[dd] - z[dd] : 0.0;
+                    q = fma(df, df, q);
+                }
+                const double e = g.sf2 * exp_rbf(g.c * q);
+                kv[ks] = i < g.nv ? e : 0.0;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const double* brow = panel + (4 * ks + kq) * kSelStride + lc;
+#pragma unroll
+                for (int t = 0; t < kSelCT; ++t)
+                    if (t >= lt0 && t < tn)
+                        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(kv[ks], brow[16 * t], acc[t], 0, 0, 0);
+            }
+        }
+        // acc[t][r] = V[candidate p0 + kq + 4r][column 16 (t0 + t) + lc]
+#pragma unroll
+        for (int t = 0; t < kSelCT; ++t) {
+            if (t < tn) {
+                double* col = g.Vt + (size_t)(16 * (t0 + t) + lc) * a.ldp;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int pr = p0 + kq + 4 * r;
+                    if (pr < a.P) col[pr] = acc[t][r];
+                }
+            }
+        }
+    }
+}
+
+// A block's best candidates: the largest finite score (ties to the lower index; idx INT_MAX: none) and the lowest
+// index among the candidates whose score is not finite (INT_MAX: none).  The order is total, so a reduction gives the
+// same result in whatever order it merges.
+struct SelectBest {
+    double val;
+    int idx, nf;
+};
+constexpr int kSelNone = 0x7fffffff;
+__device__ __forceinline__ SelectBest select_merge(const SelectBest& x, const SelectBest& y) {
+    SelectBest r = x;
+    if (y.idx != kSelNone && (x.idx == kSelNone || y.val > x.val || (y.val == x.val && y.idx < x.idx))) {
+        r.val = y.val;
+        r.idx = y.idx;
+    }
+    r.nf = min(x.nf, y.nf);
+    return r;
+}
+__device__ __forceinline__ SelectBest select_candidate(double s, int i, bool open) {
+    const bool fin = isfinite(s);
+    return SelectBest{(open && fin) ? s : 0.0, (open && fin) ? i : kSelNone, (open && !fin) ? i : kSelNone};
+}
+// over each group of kSelectBlock consecutive lanes; the group's first lane holds the result
+__device__ __forceinline__ SelectBest select_group_best(SelectBest b) {
+#pragma unroll
+    for (int off = kSelectBlock / 2; off >= 1; off >>= 1) {
+        SelectBest o;
+        o.val = __shfl_down(b.val, off, kSelectBlock);
+        o.idx = __shfl_down(b.idx, off, kSelectBlock);
+        o.nf = __shfl_down(b.nf, off, kSelectBlock);
+        b = select_merge(b, o);
+    }
+    return b;
+}
+
+// gp_score_kernel's score of candidate i from the variances d[g * ldd + i]
+__device__ __forceinline__ double select_score(const GPSelect& a, const double* d, size_t ldd, int i, bool bad_input) {
+    double s = d[i] / a.g[0].sf2;
+    for (int g = 1; g < a.n_gp; ++g) {
+        const double t = d[(size_t)g * ldd + i] / a.g[g].sf2;
+        if (t > s || t != t) s = t;   // (a NaN stays: nothing compares above it)
+    }
+    return bad_input ? __longlong_as_double(0x7ff8000000000000ll) : s;
+}
+
+// The start state: d = the variance launches' output, the non-finite inputs marked, each block's best, ok = 1.
+// One wave = 64 / kSelectBlock candidate blocks.
+__global__ __launch_bounds__(64) void gp_select_init_kernel(const GPSelect a) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const bool valid = i < a.P;
+    SelectBest b{0.0, kSelNone, kSelNone};
+    if (valid) {
+        for (int g = 0; g < a.n_gp; ++g) a.d[(size_t)g * a.ldp + i] = a.var0[(size_t)g * a.ldv + i];
+        bool finite = true;
+        for (int k = 0; k < a.ldz; ++k) finite = finite && isfinite(a.Z[(size_t)i * a.ldz + k]);
+        a.state[i] = finite ? 0 : 2;
+        b = select_candidate(select_score(a, a.var0, a.ldv, i, !finite), i, true);
+    }
+    b = select_group_best(b);
+    const int blk = i / kSelectBlock;
+    if (threadIdx.x % kSelectBlock == 0 && blk < a.nblk) {
+        a.bval[blk] = b.val;
+        a.bidx[2 * blk] = b.idx;
+        a.bidx[2 * blk + 1] = b.nf;
+    }
+    if (i == 0 && a.ok != nullptr) a.ok[0] = 1;
+}
+
+// Pick t.  Every workgroup reduces the blocks' bests of the previous launch to j_t (the same total order everywhere),
+// then conditions its kSelectBlock candidates of every GP on j_t and leaves its own best for the next launch.  A
+// workgroup is kSelectBlock candidates times kSelectParts parts of the inner product
+// v_i . v_j + sum_s l_s[i] l_s[j]: part q takes the column tiles [q nt / 16, (q + 1) nt / 16) of V (nt = npad / 16)
+// and the l columns s = q, q + 16, .., one sequential sum, and the parts are added as a balanced tree,
+// ((0 + 1) + (2 + 3)) + .. .  The split depends on npad and t only, so a candidate's values do not depend on where it
+// sits.  One step reads all of V once: with few candidates per workgroup and the loads of four columns in flight the
+// launch is spread over P / kSelectBlock workgroups instead of waiting on one chain of dependent loads.
+constexpr int kSelectParts = 16;
+constexpr int kSelThreads = kSelectBlock * kSelectParts;
+__global__ __launch_bounds__(kSelThreads) void gp_select_step_kernel(const GPSelect a, const int t) {
+    __shared__ double sval[kSelThreads];
+    __shared__ int sidx[kSelThreads], snf[kSelThreads];
+    __shared__ double part[kSelectParts][kSelectBlock];
+    const int tid = threadIdx.x;
+    const int cur = t & 1, nxt = cur ^ 1;
+    SelectBest b{0.0, kSelNone, kSelNone};
+    for (int k = tid; k < a.nblk; k += kSelThreads) {
+        const size_t at = (size_t)cur * a.nblk + k;
+        b = select_merge(b, SelectBest{a.bval[at], a.bidx[2 * at], a.bidx[2 * at + 1]});
+    }
+    sval[tid] = b.val;
+    sidx[tid] = b.idx;
+    snf[tid] = b.nf;
+    __syncthreads();
+    for (int s = kSelThreads / 2; s >= 1; s >>= 1) {
+        if (tid < s) {
+            const SelectBest r = select_merge(SelectBest{sval[tid], sidx[tid], snf[tid]},
+                                              SelectBest{sval[tid + s], sidx[tid + s], snf[tid + s]});
+            sval[tid] = r.val;
+            sidx[tid] = r.idx;
+            snf[tid] = r.nf;
+        }
+        __syncthreads();
+    }
+    const bool fin = sidx[0] != kSelNone;   // a finite candidate is left; else the non-finite ones in index order
+    const int j = fin ? sidx[0] : snf[0];
+    const double gain = sval[0];
+    if (j < 0 || j >= a.P) return;   // (m <= P leaves a candidate for every pick; uniform)
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    if (blockIdx.x == 0 && tid == 0) {
+        a.pick[t] = j;
+        if (a.gain != nullptr) a.gain[t] = fin ? gain : nan;
+    }
+    const int ci = tid % kSelectBlock, kp = tid / kSelectBlock;
+    const int i = blockIdx.x * kSelectBlock + ci;
+    const bool valid = i < a.P;
+    const int ii = valid ? i : a.P - 1;
+    const size_t ldp = a.ldp;
+    double score = 0.0;
+    for (int gi = 0; gi < a.n_gp; ++gi) {
+        const GPSelectGP& g = a.g[gi];
+        const double* din = a.d + ((size_t)cur * a.n_gp + gi) * ldp;
+        double* dout = a.d + ((size_t)nxt * a.n_gp + gi) * ldp;
+        const double pv = din[j] + g.sn2;
+        const bool good = fin && isfinite(pv) && pv > 0.0;   // (uniform over the workgroup)
+        if (fin && !good && blockIdx.x == 0 && tid == 0 && a.ok != nullptr) a.ok[0] = 0;
+        double l = 0.0;
+        if (good) {
+            const int ntile = g.npad / 16;
+            const int c0 = 16 * (kp * ntile / kSelectParts), c1 = 16 * ((kp + 1) * ntile / kSelectParts);
+            const double* vi = g.Vt + ii;
+            const double* vj = g.Vt + j;
+            double acc = 0.0;
+            for (int c = c0; c < c1; c += 4) {   // (whole tiles: c1 - c0 is a multiple of 16)
+                double x[4], y[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    x[k] = vi[(size_t)(c + k) * ldp];
+                    y[k] = vj[(size_t)(c + k) * ldp];
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc = fma(x[k], y[k], acc);
+            }
+            for (int s = kp; s < t; s += kSelectParts)
+                acc = fma(g.lcol[(size_t)s * ldp + ii], g.lcol[(size_t)s * ldp + j], acc);
+            part[kp][ci] = acc;
+            __syncthreads();
+            if (kp == 0) {
+                double r[kSelectParts];
+#pragma unroll
+                for (int q = 0; q < kSelectParts; ++q) r[q] = part[q][ci];
+#pragma unroll
+                for (int w = kSelectParts / 2; w >= 1; w >>= 1)
+#pragma unroll
+                    for (int q = 0; q < w; ++q) r[q] = r[2 * q] + r[2 * q + 1];
+                const double k = select_kernel_value(g, a.Z + (size_t)ii * a.ldz + g.zcol, a.Z + (size_t)j * a.ldz + g.zcol);
+                l = (k - r[0]) / sqrt(pv);
+            }
+            __syncthreads();
+        }
+        if (kp == 0 && valid) {
+            g.lcol[(size_t)t * ldp + i] = l;
+            const double dn = din[i] - l * l;
+            dout[i] = dn;
+            if (a.resid != nullptr && t == a.m - 1) a.resid[(size_t)gi * a.P + i] = dn;
+            const double sg = dn / g.sf2;
+            if (gi == 0 || sg > score || sg != sg) score = sg;
+        }
+    }
+    if (kp == 0) {   // (the first kSelectBlock lanes of wave 0)
+        SelectBest nb{0.0, kSelNone, kSelNone};
+        if (valid) {
+            int st = a.state[i];
+            if (i == j) a.state[i] = st = st | 1;
+            nb = select_candidate((st & 2) ? nan : score, i, !(st & 1));
+        }
+        nb = select_group_best(nb);
+        if (tid == 0) {
+            const size_t at = (size_t)nxt * a.nblk + blockIdx.x;
+            a.bval[at] = nb.val;
+            a.bidx[2 * at] = nb.idx;
+            a.bidx[2 * at + 1] = nb.nf;
+        }
+    }
+}
+
 }  // namespace
+
+hipError_t launch_gp_select(const GPSelect& a, hipStream_t stream) {
+    if (a.P < 1 || a.m < 1 || a.m > a.P || a.m > kSelectMaxPicks || a.P > a.ldp || a.n_gp < 1 || a.n_gp > kMaxGP ||
+        a.nblk != (a.P + kSelectBlock - 1) / kSelectBlock)
+        return hipErrorInvalidValue;
+    for (int g = 0; g < a.n_gp; ++g)
+        if (a.g[g].npad < 16 || a.g[g].npad % 16 != 0 || a.g[g].nv > a.g[g].npad) return hipErrorInvalidValue;
+    GP_LAUNCH(gp_select_v_kernel, dim3((a.P + 16 * kSelWaves - 1) / (16 * kSelWaves), a.n_gp), dim3(64 * kSelWaves), stream, a);
+    GP_LAUNCH(gp_select_init_kernel, dim3((a.P + 63) / 64), dim3(64), stream, a);
+    for (int t = 0; t < a.m; ++t) GP_LAUNCH(gp_select_step_kernel, dim3(a.nblk), dim3(kSelThreads), stream, a, t);
+    return hipSuccess;
+}
 
 hipError_t launch_gp_observe(const GPObserve& a, hipStream_t stream) {
     const dim3 grid((a.m + kObserveThreads - 1) / kObserveThreads), block(kObserveThreads);

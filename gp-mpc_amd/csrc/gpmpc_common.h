@@ -481,6 +481,42 @@ struct GPRank {
     int32_t* pick;        // [m]
 };
 hipError_t launch_gp_score_rank(const GPRank& a, hipStream_t stream);
+// Greedy conditional-variance selection of m of P candidates (gp_observe.hip; gpmpc_gp_select fills it): a pivoted
+// partial Cholesky of the candidates' posterior covariance, every GP conditioned on each pick observed with its
+// likelihood noise.  var0 holds the start variances d_g,i (the variance launches' own output); everything else is
+// scratch of the handle.  Candidate i's entries of V, of the l columns and of d lie at [.][i] with stride ldp, so the
+// pick loop reads them coalesced over the candidates.
+constexpr int kSelectMaxPicks = 256;
+constexpr int kSelectBlock = 16;      // candidates per workgroup of the pick loop
+struct GPSelectGP {
+    const double* rows;   // GPDev::vrows [>= npad][4]
+    const double* linvT;  // [npad][npad]
+    double* Vt;           // [npad][ldp]: Vt[c][i] = (L^-1 k(X, z_i))_c
+    double* lcol;         // [kSelectMaxPicks][ldp]: l_t[i]
+    int32_t npad, nv, d;
+    int32_t zcol;         // the GP's first column in the gathered inputs
+    double c, sf2, sn2;   // c = -1 / (2 ell^2)
+};
+struct GPSelect {
+    int32_t P, m, n_gp;
+    int32_t ldp;          // stride of the per-candidate arrays (>= P)
+    int32_t nblk;         // ceil(P / kSelectBlock)
+    const double* Z;      // [P][ldz] the candidates' gathered GP inputs
+    int32_t ldz;
+    const double* var0;   // [n_gp][ldv]
+    int32_t ldv;
+    GPSelectGP g[kMaxGP];
+    double* d;            // [2][n_gp][ldp]: step t reads half t & 1 and writes the other
+    int32_t* state;       // [ldp]: bit 0 picked, bit 1 a non-finite GP input
+    double* bval;         // [2][nblk]: each block's best finite score among its unpicked candidates
+    int32_t* bidx;        // [2][nblk][2]: its index (INT_MAX: none), the block's lowest unpicked non-finite candidate
+    int32_t* pick;        // [m]
+    double* gain;         // [m] or null
+    double* resid;        // [n_gp][P] or null
+    int32_t* ok;          // [1] or null
+};
+// V for every GP (one launch), the start state, then one launch per pick
+hipError_t launch_gp_select(const GPSelect& a, hipStream_t stream);
 hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream);
 hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream);
 hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream);

@@ -62,6 +62,7 @@ SIGNATURES = {
     "gpmpc_plant_step": (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
     "gpmpc_preprocess": (_I, [_P, _I, _P, _P, _P, _I, _P, _D, _D, _P, _P, _P]),
     "gpmpc_gp_informative": (_I, [_P, _I, _P, _P, _I, _P, _P, _P]),
+    "gpmpc_gp_select": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     "gpmpc_gp_observe": (_I, [_P, _I, _P, _P, _P, _I, _P, _D, _D, _I, _P, _P, _P, _P, _P]),
     "gpmpc_set_launch": (_I, [_P, _I]),
     "gpmpc_set_profiling": (_I, [_P, _I]),

@@ -332,20 +332,22 @@ class GPMPC:
 
         ``select=None``: the rows are the transitions ``pick`` names (int32 indices), or the first ``m`` (default
         all).  ``select="variance"``: the ``m`` transitions where the GPs are least certain
-        (``BatchSolver.informative``; at most ``batch`` transitions).  ``evict_oldest``, the capacity check, the
+        (``BatchSolver.informative``; at most ``batch`` transitions).  ``select="greedy"``: ``m`` <= 256 transitions
+        chosen one after the other, each the least certain once the ones before it count as observed
+        (``BatchSolver.select``), so a step's near-duplicates are not all taken.  ``evict_oldest``, the capacity check, the
         LOVE roots, the device-built FITC means and the refusals in sparse mode are ``append_data``'s.  Returns
         ``(inputs, targets, accepted, dropped_ok)`` as ``BatchSolver.observe`` does."""
         if self.sparse and self.fitc != "device":
             raise _lib.GPMPCError("observe: not available in sparse (FITC) mode")
         assert self.gaussian_process is not None and not self._requires_recompile, \
             "GP model must be uploaded (call reset())"
-        if select not in (None, "variance"):
-            raise ValueError("select must be None or 'variance'")
+        if select not in (None, "variance", "greedy"):
+            raise ValueError("select must be None, 'variance' or 'greedy'")
         s = self.solver
         x, u, x_next = s._transitions(x, u, x_next)
-        if select == "variance":
+        if select is not None:
             if pick is not None or m is None:
-                raise ValueError("select='variance' chooses the rows itself: pass m, not pick")
+                raise ValueError(f"select='{select}' chooses the rows itself: pass m, not pick")
             rows = int(m)
         else:
             pick, rows = s._picks(pick, m, x.shape[0])
@@ -357,7 +359,7 @@ class GPMPC:
                                   "construct GPMPC with gp_capacity)")
 
         def update():
-            p = s.informative(x, u, rows) if select == "variance" else pick
+            p = s.informative(x, u, rows) if select == "variance" else s.select(x, u, rows)[0] if select == "greedy" else pick
             out = s.observe(x, u, x_next, pick=p, m=rows, evict_oldest=evict_oldest)
             inputs, targets = out[0], out[1]
             for i, idx in enumerate(self.gp_idx):

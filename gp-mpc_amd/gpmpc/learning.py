@@ -78,14 +78,15 @@ def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, s
     picks, with the same call and seed as the host path, so both paths learn from the same transitions;
     the only upload per step is those picks, an int32 index tensor.  ``select="variance"`` (needs
     ``device_data=True``) picks the step's transitions where the GPs are least certain instead
-    (``BatchSolver.informative``) and uploads nothing.  The two paths differ by rounding in the targets.
+    (``BatchSolver.informative``) and uploads nothing; ``select="greedy"`` (likewise) picks them one after the other,
+    each conditioned on the ones before it (``BatchSolver.select``).  The two paths differ by rounding in the targets.
 
     Returns the dict of :func:`run_evaluation` plus ``n_train`` (steps,), the training rows after
     each step; with ``device_data=True`` also ``pick``, the list of every step's picked indices."""
-    if select not in ("random", "variance"):
-        raise ValueError("select must be 'random' or 'variance'")
-    if select == "variance" and not device_data:
-        raise ValueError("select='variance' picks on the device: it needs device_data=True")
+    if select not in ("random", "variance", "greedy"):
+        raise ValueError("select must be 'random', 'variance' or 'greedy'")
+    if select != "random" and not device_data:
+        raise ValueError(f"select='{select}' picks on the device: it needs device_data=True")
     if device_data:
         return _run_online_episode_device(ctrl, x0, steps, append_per_step, seed, tstep0, sliding, refresh_every, select)
     ctrl.reset()
@@ -157,7 +158,8 @@ def _run_online_episode_device(ctrl, x0, steps, append_per_step, seed, tstep0, s
             pick = np.zeros(0, dtype=np.int32)
             if m:
                 # (the indices are read back after the episode; the rows they name are the appended inputs)
-                pick = solver.informative(obs[step], action[step], m)
+                pick = (solver.informative(obs[step], action[step], m) if select == "variance"
+                        else solver.select(obs[step], action[step], m)[0])
                 ctrl.observe(obs[step], action[step], obs[step + 1], pick=pick, evict_oldest=sliding)
             picks.append(pick)
         if refresh_every > 0 and (step + 1) % refresh_every == 0:

@@ -268,6 +268,25 @@ class BatchSolver:
                                                  _lib.ptr(score), self._stream()))
         return (pick, score) if scores else pick
 
+    def select(self, x, u, m: int, gains: bool = False, resid: bool = False):
+        """Greedy conditional-variance selection of ``m`` <= 256 of the P <= batch points (gpmpc_gp_select): each
+        pick is the point with the largest score of ``informative`` once the picks before it count as observed
+        (with the likelihood noise), so near-duplicates of a pick are not picked after it.  Pick 0 and its gain are
+        ``informative``'s top pick and score, bit for bit.  Returns the device int32 picks (m,), then with
+        ``gains=True`` the (m,) scores at which they were picked, with ``resid=True`` the (n_gp, P) posterior
+        variances (no noise) of the GPs with the picks added, and last the int32 flag tensor [1] (0: a pivot was not
+        finite and positive, and that GP skipped that pick).  On the current stream, no synchronisation of its own;
+        nothing of the GPs changes."""
+        x, u = self._transitions(x, u)
+        P = x.shape[0]
+        pick = torch.empty(max(int(m), 0), dtype=torch.int32, device=self.device)
+        gain = torch.empty(max(int(m), 0), dtype=torch.float64, device=self.device) if gains else None
+        res = torch.empty(self.spec.n_gp, P, dtype=torch.float64, device=self.device) if resid else None
+        ok = torch.empty(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gpmpc_gp_select(self._h, P, x.data_ptr(), u.data_ptr(), int(m), pick.data_ptr(),
+                                            _lib.ptr(gain), _lib.ptr(res), ok.data_ptr(), self._stream()))
+        return tuple(t for t in (pick, gain, res, ok) if t is not None)
+
     def observe(self, x, u, x_next, pick=None, m=None, evict_oldest: bool = False):
         """``preprocess`` followed by an append of the m rows to every GP of the handle, in one call on the
         current stream (gpmpc_gp_observe; m <= batch): bit-identical to ``preprocess``, a column slice per GP,

@@ -390,13 +390,43 @@ gpmpc_status gpmpc_preprocess(gpmpc_handle* h, int32_t P, const double* x_dev, c
  * lower index, and a score that is not finite ranks after every finite one, again lower index first.  The rank
  * is counted (rank_i = the number of points that beat i, O(P^2) comparisons), so every output is fixed bit for
  * bit.  score_dev (device float64 [P]) receives the scores, may be NULL.  The picks are the m most uncertain
- * points one by one: no account is taken of redundancy among them, and near-duplicates may all be picked.
+ * points one by one: no account is taken of redundancy among them, and near-duplicates may all be picked;
+ * gpmpc_gp_select below conditions every candidate on the picks before it and so picks no near-duplicates.
  * Asynchronous on `stream`, no host synchronisation; the first call allocates the handle's scratch for max_batch
  * points, a synchronous setup step like gpmpc_gp_reserve.
  * Refused: P < 1, P > max_batch, m < 1, m > P, NULL x_dev, u_dev or pick_dev (GPMPC_ERR_ARG); a GP of the model
  * not set, or set without Linv (GPMPC_ERR_STATE). */
 gpmpc_status gpmpc_gp_informative(gpmpc_handle* h, int32_t P, const double* x_dev, const double* u_dev, int32_t m,
                                   int32_t* pick_dev, double* score_dev, void* stream);
+
+/* Greedy conditional-variance selection: m of the P candidates z_i = [x_i; u_i] (device, as above) such that each
+ * pick is the candidate the GPs are least certain about once the picks before it are taken as observed.  This is a
+ * pivoted partial Cholesky of the candidates' posterior covariance.  For each GP g, from the exact factor the handle
+ * holds: v_g,i = L_g^-1 k_g(X_g, z_i) and d_g,i = outputscale_g - |v_g,i|^2, the latter the variance launches of
+ * gpmpc_gp_informative (the same bits).  Then for t = 0 .. m-1:
+ *   score    s_i = max_g d_g,i / outputscale_g over the candidates not yet picked, NaN for a candidate with a
+ *            non-finite GP input or a NaN variance (gpmpc_gp_informative's rule);
+ *   pick     j_t = the largest finite score, ties to the lower index: pick_dev[t] = j_t, gain_dev[t] = s_{j_t}.  When
+ *            no finite candidate is left the remaining picks are the non-finite ones in index order, with gain NaN,
+ *            and they condition nothing;
+ *   condition, per GP: p = d_g,j + noise_g,
+ *            l_g,t[i] = (k_g(z_i, z_j) - v_g,i . v_g,j - sum_{s<t} l_g,s[i] l_g,s[j]) / sqrt(p),
+ *            d_g,i -= l_g,t[i]^2 for every i.  A p that is not finite and positive skips GP g for this pick and
+ *            clears ok_dev[0], which is otherwise written as 1.
+ * So step 0 is gpmpc_gp_informative's top pick and score, bit for bit, and afterwards the d_g,i are the posterior
+ * variances (without noise) of a GP with the picked rows appended.  pick_dev: device int32 [m].  gain_dev (device
+ * float64 [m]), resid_dev (device float64 [n_gp][P]: the final d_g,i; the entry of a non-finite candidate is
+ * unspecified) and ok_dev (device int32 [1]) may be NULL.  Every output is fixed bit for bit by the inputs (fixed
+ * summation orders, no atomics), and what is computed for a candidate depends on its own inputs and the GPs only:
+ * duplicated candidates carry equal bits.  A LOVE root and a FITC mean are ignored, inert rows take no part, nothing
+ * of the GPs changes.
+ * Asynchronous on `stream`, no host synchronisation: the variance launches, one launch that stores V for every GP,
+ * one for the start state and one per pick.  The handle's scratch (V at the GPs' capacity, the l columns
+ * [n_gp][256][max_batch]) is allocated by the first call and again when a capacity has grown, a synchronous setup
+ * step like gpmpc_gp_reserve; if that fails the call returns GPMPC_ERR_NOMEM and the handle is unchanged.
+ * Refused: as gpmpc_gp_informative, and m > 256 (GPMPC_ERR_ARG). */
+gpmpc_status gpmpc_gp_select(gpmpc_handle* h, int32_t P, const double* x_dev, const double* u_dev, int32_t m,
+                             int32_t* pick_dev, double* gain_dev, double* resid_dev, int32_t* ok_dev, void* stream);
 
 /* gpmpc_preprocess followed by an append of the m rows to every GP of the handle, in one stream-ordered call:
  * the rows are staged per GP (X_g [m][d_g], y_g [m]) in scratch of the handle, which holds max_batch rows and is

@@ -16,6 +16,18 @@ the median run's ms per step for each side (a run's figure is the median over it
 ratio of the medians, and the solve's ms per step for scale.
 
     python tools/observe_ab.py                 # quad2d B=1024 H=30 capacity 400, 16 rows per step
+
+`--select` changes the axis: every side is the device path, and the sides differ in who picks the step's rows.
+
+    random    the host generator's picks, uploaded (the device side above)
+    variance  GPMPC.observe(select="variance"): gpmpc_gp_informative, the top rows by variance one by one
+    greedy    GPMPC.observe(select="greedy"): gpmpc_gp_select, each row conditioned on the rows before it
+
+    python tools/observe_ab.py --select variance greedy
+
+alternates the sides named, in the order given, and prints the same figures per side, the ratio of the last side's
+median to the first's and the launches one selection queues (the gather, a variance launch per GP, and for greedy
+the V launch, the start state and one launch per row).
 """
 
 from __future__ import annotations
@@ -35,7 +47,7 @@ for p in (ROOT / "gp-mpc_amd", ROOT):
         sys.path.insert(0, str(p))
 
 
-def run(args, torch, device_data: bool) -> dict:
+def run(args, torch, device_data: bool, select: str = "random") -> dict:
     from gpmpc.gp import GaussianProcess
     from gpmpc.gpmpc import GPMPC
     from gpmpc.synthetic import DEFAULT_HYPERS, initial_states, make_training_data
@@ -73,7 +85,10 @@ def run(args, torch, device_data: bool) -> dict:
         torch.cuda.synchronize(dev)
         t2 = time.perf_counter()
         # ---- the learning part
-        if device_data:
+        if device_data and select != "random":
+            action[step].copy_(u)
+            ctrl.observe(obs[step], action[step], obs[step + 1], m=min(args.rows, B), select=select, evict_oldest=True)
+        elif device_data:
             action[step].copy_(u)
             pick = rng.choice(B, min(args.rows, B), replace=False)
             ctrl.observe(obs[step], action[step], obs[step + 1], pick=torch.as_tensor(pick.astype(np.int32)).to(dev),
@@ -105,12 +120,16 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--seed", type=int, default=11)
+    ap.add_argument("--select", nargs="+", choices=("random", "variance", "greedy"), default=None,
+                    help="compare these selections on the device path instead of host against device")
     args = ap.parse_args(argv)
 
     import torch
 
     if not torch.cuda.is_available():
         raise SystemExit("observe_ab.py measures on the GPU: no HIP device available")
+    if args.select:
+        return main_select(args, torch)
     runs = {False: [], True: []}
     for _ in range(args.repeats):
         for device_data in (False, True):
@@ -123,6 +142,28 @@ def main(argv=None):
         med["learn_ms_per_step_runs"] = [round(r["learn_ms_per_step"], 4) for r in runs[device_data]]
         out[name] = med
     out["host_over_device"] = out["host"]["learn_ms_per_step"] / out["device"]["learn_ms_per_step"]
+    print(json.dumps(out))
+
+
+def main_select(args, torch):
+    from gpmpc.models import get_spec
+
+    runs = {name: [] for name in args.select}
+    for _ in range(args.repeats):
+        for name in args.select:
+            runs[name].append(run(args, torch, True, name))
+    out = {"config": {k: getattr(args, k) for k in ("model", "horizon", "batch", "capacity", "rows", "steps", "warmup",
+                                                     "repeats", "seed", "select")}}
+    n_gp, m = get_spec(args.model).n_gp, min(args.rows, args.batch)
+    launches = {"random": 0, "variance": 1 + n_gp + 2, "greedy": 1 + n_gp + 2 + m}
+    for name in args.select:
+        rs = sorted(runs[name], key=lambda r: r["learn_ms_per_step"])
+        med = dict(rs[len(rs) // 2])
+        med["learn_ms_per_step_runs"] = [round(r["learn_ms_per_step"], 4) for r in runs[name]]
+        med["selection_launches"] = launches[name]
+        out[name] = med
+    first, last = args.select[0], args.select[-1]
+    out[f"{last}_over_{first}"] = out[last]["learn_ms_per_step"] / out[first]["learn_ms_per_step"]
     print(json.dumps(out))
 
 
