@@ -100,10 +100,12 @@ struct GPSlot {
 struct AppendLayout {   // W^T [16][c] | per-tile means [c/16][16] | L_b^-1 [256] | beta [16] | status word
     size_t c, wt = 0, pmean = 16 * c, lbinv = pmean + c, beta = lbinv + 256, flag = beta + 16, end = flag + 1;
 };
-// V^T [16][c] | M21 g [c] | E_T, D_T [c/16][256] each | staged rows [c][4], tX, tW [c/16][64] each | status word
+// V^T [16][c] | M21 g [c] | E_T, D_T [c/16][256] each | staged rows [c][4], tX, tW [c/16][64] each | status word |
+// gpmpc_gp_drop_rows: the sorted rows [c] and the membership mask [c] int32 (in c/2 doubles each) | the call's status
 struct DropLayout {
     size_t c, vt = 0, w = 16 * c, et = w + c, dt = et + 16 * c, srows = dt + 16 * c, stX = srows + 4 * c,
-              stW = stX + 4 * c, flag = stW + 4 * c, end = flag + 1;
+              stW = stX + 4 * c, flag = stW + 4 * c, sorted = flag + 1, mask = sorted + c / 2, acc = mask + c / 2,
+              end = acc + 1;
 };
 // L_kk^-1 [c/16][256] | w [c] | masked targets [c] | the inert mask [c] int32 (in c/2 doubles) | status word
 struct RefactorLayout {
@@ -161,9 +163,16 @@ struct SelectLayout {
         end = state + ldp / 2;
     }
 };
+// Scratch of gpmpc_gp_redundant for g GPs of at most ldn (padded) rows and mcap picks, in doubles: the c columns
+// [g][mcap][ldn] | p [2][g][ldn] | the blocks' best scores [2][nblk] | their indices [2][nblk][2] int32 | the rows'
+// state [ldn] int32
+struct RedundantLayout {
+    size_t ldn, mcap, g, nblk = ldn / kRedundantBlock, ccol = 0, p = g * mcap * ldn, bval = p + 2 * g * ldn,
+                         bidx = bval + 2 * nblk, state = bidx + 2 * nblk, end = state + ldn / 2;
+};
 constexpr bool layouts_hold(size_t c) {
     return AppendLayout{c}.end == 16 * c + c + 256 + 16 + 1 && AppendLayout{c}.flag == 17 * c + 272 &&
-           DropLayout{c}.end == 61 * c + 1 && DropLayout{c}.srows == 49 * c && RefactorLayout{c}.mask == 18 * c &&
+           DropLayout{c}.flag == 61 * c && DropLayout{c}.end == 62 * c + 2 && DropLayout{c}.srows == 49 * c && RefactorLayout{c}.mask == 18 * c &&
            RefactorLayout{c}.end == 18 * c + c / 2 + 1 && LoveLayout{c}.v == 256 * c &&
            LoveLayout{c}.end == 257 * c + c / 2 + c / 16 + 513 * ((c + 63) / 64) + (c + 255) / 256 + 4 * 256 + 4;
 }
@@ -214,6 +223,8 @@ struct gpmpc_handle {
     double* obs = nullptr;          // scratch of gpmpc_gp_informative / gpmpc_gp_observe (ObserveLayout), on first use
     double* sel = nullptr;          // scratch of gpmpc_gp_select (SelectLayout), on first use and when a capacity has grown
     size_t sel_rows[kMaxGP] = {0, 0, 0, 0};   // the padded rows its V regions were sized for
+    double* red = nullptr;          // scratch of gpmpc_gp_redundant (RedundantLayout), on first use and when a capacity has grown
+    size_t red_rows = 0, red_m = 0; // the padded rows and the picks it was sized for
     // the batch whose tightening variances the last solve's variance launch wrote into `var`
     // (0: the last solve ran none, var is stale or unset)
     int var_batch = 0;
@@ -346,6 +357,7 @@ static void free_handle(gpmpc_handle* h) {
     if (h->scratch_d) (void)hipFree(h->scratch_d);
     if (h->obs) (void)hipFree(h->obs);
     if (h->sel) (void)hipFree(h->sel);
+    if (h->red) (void)hipFree(h->red);
     for (GPSlot& gs : h->gp) (void)gs.release(GPSlot::kBuffers);
     delete h;
 }
@@ -768,26 +780,17 @@ gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const do
     return GPMPC_OK;
 }
 
-gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int32_t* ok_dev, void* stream) {
-    const gpmpc_status ready = gp_update_ready(h, gp_id, kDrop, nullptr);
-    if (ready != GPMPC_OK) return ready;
+// One block of mb <= 16 rows of GP gp_id queued on s: the oldest (didx null, ok the block's status word) or the
+// ascending rows didx names in the GP's drop scratch (ok the call's status word)
+static gpmpc_status queue_drop_block(gpmpc_handle* h, int gp_id, int mb, const int32_t* didx, int32_t* ok, hipStream_t s) {
     GPSlot& gs = h->gp[gp_id];
     GPDev& g = h->P.gp[gp_id];
-    if (m < 1) return fail(GPMPC_ERR_ARG, "no rows to drop");
-    if (m >= g.n)
-        return fail(GPMPC_ERR_ARG, "at least one row stays: " + std::to_string(m) + " of " + std::to_string(g.n) +
-                                       " rows asked for");
-    (void)hipSetDevice(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(order_after_last(h, s));
-    StreamMark mark{h, s};
     const int cpad = (gs.cap + 15) / 16 * 16, ct = cpad / 16, d = h->md.gp_dim[gp_id];
     const DropLayout lay{(size_t)cpad};
     double* rows = gs.rows;
     double* tX = gs.tiles;
     double* tW = gs.tiles + (size_t)ct * 64;
-    for (int done = 0, blk = 0; done < m; done += 16, ++blk) {
-        const int mb = std::min(16, m - done);
+    {
         const int n0 = g.n, npad0 = gs.npad, n1 = n0 - mb, npad1 = (n1 + 15) / 16 * 16;
         // the model changes with the first launch queued: the cache must not serve its old rows
         bump_lin(h);
@@ -811,7 +814,9 @@ gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int
         a.stX = gs.drp + lay.stX;
         a.stW = gs.drp + lay.stW;
         a.flag = reinterpret_cast<int32_t*>(gs.drp + lay.flag);
-        a.ok = ok_dev ? ok_dev + blk : nullptr;
+        a.ok = ok;
+        a.didx = didx;
+        a.acc = didx ? reinterpret_cast<int32_t*>(gs.drp + lay.acc) : nullptr;
         HIPCHK(launch_gp_drop(a, s));
         // the staged rows and tile pack replace the live ones (disjoint buffers); what lies between the
         // new and the old padded size becomes what rows past n always are: zero
@@ -830,6 +835,60 @@ gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int
         gs.npad = npad1;
         g.n = g.nv = n1;
         g.ntile = (n1 + 15) / 16;
+    }
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int32_t* ok_dev, void* stream) {
+    const gpmpc_status ready = gp_update_ready(h, gp_id, kDrop, nullptr);
+    if (ready != GPMPC_OK) return ready;
+    GPDev& g = h->P.gp[gp_id];
+    if (m < 1) return fail(GPMPC_ERR_ARG, "no rows to drop");
+    if (m >= g.n)
+        return fail(GPMPC_ERR_ARG, "at least one row stays: " + std::to_string(m) + " of " + std::to_string(g.n) +
+                                       " rows asked for");
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    for (int done = 0, blk = 0; done < m; done += 16, ++blk) {
+        const gpmpc_status st = queue_drop_block(h, gp_id, std::min(16, m - done), nullptr, ok_dev ? ok_dev + blk : nullptr, s);
+        if (st != GPMPC_OK) return st;
+    }
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_drop_rows(gpmpc_handle* h, int32_t gp_id, int32_t m, const int32_t* idx_dev, int32_t* dropped_dev,
+                                int32_t* ok_dev, void* stream) {
+    const gpmpc_status ready = gp_update_ready(h, gp_id, kDrop, nullptr);
+    if (ready != GPMPC_OK) return ready;
+    GPSlot& gs = h->gp[gp_id];
+    GPDev& g = h->P.gp[gp_id];
+    if (m < 1 || !idx_dev) return fail(GPMPC_ERR_ARG, "no rows to drop");
+    if (m >= g.n)
+        return fail(GPMPC_ERR_ARG, "at least one row stays: " + std::to_string(m) + " of " + std::to_string(g.n) +
+                                       " rows asked for");
+    (void)hipSetDevice(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const DropLayout lay{(size_t)((gs.cap + 15) / 16 * 16)};
+    int32_t* sorted = reinterpret_cast<int32_t*>(gs.drp + lay.sorted);
+    GPDropPrep p{};
+    p.idx = idx_dev;
+    p.n = g.n;
+    p.m = m;
+    p.mask = reinterpret_cast<int32_t*>(gs.drp + lay.mask);
+    p.sorted = sorted;
+    p.dropped = dropped_dev;
+    p.acc = reinterpret_cast<int32_t*>(gs.drp + lay.acc);
+    HIPCHK(launch_gp_drop_prep(p, s));
+    // from the highest rows down, so no block shifts the rows of the blocks after it
+    for (int left = m; left > 0;) {
+        const int mb = std::min(16, left);
+        left -= mb;
+        const gpmpc_status st = queue_drop_block(h, gp_id, mb, sorted + left, ok_dev, s);
+        if (st != GPMPC_OK) return st;
     }
     return GPMPC_OK;
 }
@@ -2068,6 +2127,69 @@ gpmpc_status gpmpc_gp_select(gpmpc_handle* h, int32_t P, const double* x_dev, co
     q.resid = resid_dev;
     q.ok = ok_dev;
     HIPCHK(launch_gp_select(q, s));
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_redundant(gpmpc_handle* h, int32_t m, int32_t* pick_dev, double* score_dev, int32_t* ok_dev,
+                                void* stream) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    if (!pick_dev) return fail(GPMPC_ERR_ARG, "null picks");
+    const int ngp = h->md.ngp;
+    size_t rows = 0;
+    for (int g = 0; g < ngp; ++g) {
+        const GPSlot& gs = h->gp[g];
+        if (!gs.set) return fail(GPMPC_ERR_STATE, "GP not set (gpmpc_set_gp first)");
+        if (!gs.exact) return fail(GPMPC_ERR_STATE, "FITC upload (Xv != X): only an exact GP has its rows ranked");
+        if (!gs.linvT) return fail(GPMPC_ERR_STATE, "the precision needs Linv (the GP was set without it)");
+        rows = std::max(rows, (size_t)std::max((gs.cap + 15) / 16 * 16, gs.npad));
+    }
+    const int n = h->P.gp[0].nv;
+    for (int g = 1; g < ngp; ++g)
+        if (h->P.gp[g].nv != n)
+            return fail(GPMPC_ERR_STATE, "the GPs differ in their training rows: the call ranks the same rows in all");
+    if (m < 1 || m >= n)
+        return fail(GPMPC_ERR_ARG, "m must be in 1 .. n - 1 (at least one row stays): " + std::to_string(m) + " of " +
+                                       std::to_string(n) + " rows asked for");
+    if (m > kRedundantMaxPicks) return fail(GPMPC_ERR_ARG, "m must be at most " + std::to_string(kRedundantMaxPicks));
+    (void)hipSetDevice(h->device);
+    // the scratch: made by the first call and made again when a capacity or the picks have grown past it (a
+    // synchronous setup step); a failed allocation leaves the handle as it was
+    if (!h->red || rows > h->red_rows || (size_t)m > h->red_m) {
+        const size_t want_rows = std::max(rows, h->red_rows), want_m = std::max(((size_t)m + 15) / 16 * 16, h->red_m);
+        double* fresh = nullptr;
+        const hipError_t e = hipMalloc(&fresh, RedundantLayout{want_rows, want_m, (size_t)ngp}.end * sizeof(double));
+        if (e != hipSuccess) return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+        if (h->red) (void)hipFree(h->red);   // (waits for the work queued on it)
+        h->red = fresh;
+        h->red_rows = want_rows;
+        h->red_m = want_m;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const RedundantLayout lay{h->red_rows, h->red_m, (size_t)ngp};
+    GPRedundant q{};
+    q.n = n;
+    q.m = m;
+    q.n_gp = ngp;
+    q.ldn = (int)lay.ldn;
+    q.nblk = (n + kRedundantBlock - 1) / kRedundantBlock;
+    for (int g = 0; g < ngp; ++g) {
+        GPRedundantGP& rg = q.g[g];
+        rg.linvT = h->P.gp[g].linvT;
+        rg.ccol = h->red + lay.ccol + (size_t)g * lay.mcap * lay.ldn;
+        rg.npad = h->gp[g].npad;
+        rg.sf2 = h->P.gp[g].sf2;
+        rg.sn2 = h->P.gp[g].sn2;
+    }
+    q.p = h->red + lay.p;
+    q.bval = h->red + lay.bval;
+    q.bidx = reinterpret_cast<int32_t*>(h->red + lay.bidx);
+    q.state = reinterpret_cast<int32_t*>(h->red + lay.state);
+    q.pick = pick_dev;
+    q.score = score_dev;
+    q.ok = ok_dev;
+    HIPCHK(launch_gp_redundant(q, s));
     return GPMPC_OK;
 }
 

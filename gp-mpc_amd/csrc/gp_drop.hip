@@ -228,14 +228,487 @@ __global__ __launch_bounds__(64 * kDropWaves) void gp_drop_apply_kernel(GPDrop a
     }
 }
 
+// ---------------------------------------------------------------------------- arbitrary rows (gpmpc_gp_drop_rows)
+// D: the block's m <= 16 rows, ascending; k: the kept rows in their old order.  M[D, k] is no longer zero (entry
+// (d, j) is non-zero for j < d), so the trailing factor is first restored and then updated as above:
+//
+//   V = -M[k, D] M[D, D]^-1,  B = M[k, k] + V M[D, k]  (= L[k, k]^-1, lower triangular),  M' = C^-1 B
+//   g = P[D, D]^-1 alpha[D],  u = M[:, D] g  (all n rows),  alpha'_c = alpha[k_c] - linvT[k_c] . u
+//
+// with G_T, E_T, D_T, S_T unchanged: gp_drop_tile_kernel serves both.  The head and the apply kernel read the old
+// factor through the kept-row map, which needs no array (drop_kept_row); the apply kernel's B tiles carry the rank-m
+// term V_T M[D, k], one more 16 x 16 x 16 product per tile.  For D = {0 .. m-1} every formula is the one above.
+// A call's rows are sorted once (gp_drop_prep_kernel) and its blocks taken from the highest indices down, so no
+// block shifts the indices of the blocks after it.
+
+// The old index of kept row c when the ascending rows d[0 .. m-1] leave
+__device__ __forceinline__ int drop_kept_row(const int (&d)[16], int m, int c) {
+    int i = c;
+#pragma unroll
+    for (int b = 0; b < 16; ++b)
+        if (b < m && d[b] <= i) ++i;
+    return i;
+}
+// The block's rows, held to 0 .. n0-1 whatever the scratch holds (entries past m: 0)
+__device__ __forceinline__ int drop_row_at(const GPDrop& a, int b) {
+    return b < a.m ? min(max(a.didx[b], 0), a.n0 - 1) : 0;
+}
+__device__ __forceinline__ void drop_rows_load(const GPDrop& a, int (&d)[16]) {
+#pragma unroll
+    for (int b = 0; b < 16; ++b) d[b] = drop_row_at(a, b);
+}
+
+// The flags set in the threads before this one (workgroup of 256) and their total
+__device__ __forceinline__ int prep_rank(bool f, int tid, int* wsum, int& total) {
+    const unsigned long long bal = __ballot(f);
+    const int lane = tid & 63, wave = tid >> 6;
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    __syncthreads();   // the previous call's sums have been read
+    if (lane == 0) wsum[wave] = __popcll(bal);
+    __syncthreads();
+    int base = 0;
+    total = 0;
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) base += wsum[w];
+        total += wsum[w];
+    }
+    return base + before;
+}
+
+// One workgroup: the membership mask of the indices in range, the lowest free rows added while fewer than m are
+// marked, and the marked rows written in ascending order.
+__global__ __launch_bounds__(256) void gp_drop_prep_kernel(GPDropPrep a) {
+    __shared__ int wsum[4];
+    __shared__ int bad;
+    const int tid = threadIdx.x;
+    if (tid == 0) bad = 0;
+    for (int i = tid; i < a.n; i += 256) a.mask[i] = 0;
+    __syncthreads();
+    for (int k = tid; k < a.m; k += 256) {
+        const int v = a.idx[k];
+        if (v >= 0 && v < a.n) a.mask[v] = 1;   // (duplicates write the same value)
+        else bad = 1;
+    }
+    __syncthreads();
+    int count = 0;
+    for (int i0 = 0; i0 < a.n; i0 += 256) {
+        int total;
+        const int i = i0 + tid;
+        (void)prep_rank(i < a.n && a.mask[i] != 0, tid, wsum, total);
+        count += total;
+    }
+    const int deficit = a.m - count;   // (the same in every thread)
+    int seen = 0;
+    for (int i0 = 0; i0 < a.n && seen < deficit; i0 += 256) {
+        int total;
+        const int i = i0 + tid;
+        const bool f = i < a.n && a.mask[i] == 0;
+        const int r = prep_rank(f, tid, wsum, total);
+        if (f && seen + r < deficit) a.mask[i] = 1;
+        seen += total;
+    }
+    __syncthreads();
+    int at = 0;
+    for (int i0 = 0; i0 < a.n; i0 += 256) {
+        int total;
+        const int i = i0 + tid;
+        const bool f = i < a.n && a.mask[i] != 0;
+        const int r = prep_rank(f, tid, wsum, total);
+        if (f && at + r < a.m) {
+            a.sorted[at + r] = i;
+            if (a.dropped != nullptr) a.dropped[at + r] = i;
+        }
+        at += total;
+    }
+    if (tid == 0) *a.acc = (bad == 0 && deficit == 0) ? 1 : 0;
+}
+
+// gp_drop_head_kernel through the row set: M[D, D] and its inverse, P[D, D] and g; then u over all old rows and V^T
+// over the kept ones.
+__global__ __launch_bounds__(256) void gp_drop_rows_head_kernel(GPDrop a) {
+    __shared__ double A[16][17], Li[16][17], P[16][17], gv[16], tmp[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lc = lane & 15, kq = lane >> 4;
+    const int m = a.m, n2 = a.n0 - a.m;
+    int d[16];
+    drop_rows_load(a, d);
+    {   // M[D, D] padded with the identity; an inert row's zero diagonal reads as 1
+        const int p = tid >> 4, q = tid & 15;
+        double v = (p == q) ? 1.0 : 0.0;
+        if (p < m && q <= p) {
+            v = a.src[(size_t)drop_row_at(a, q) * a.npad0 + drop_row_at(a, p)];
+            if (p == q && v == 0.0) v = 1.0;
+        }
+        A[p][q] = v;
+        Li[p][q] = 0.0;
+    }
+    if (wave == 0) {
+        // P[D, D] = Gram matrix of the rows D of linvT
+        const f64x4 g = gram16(a.src + (size_t)drop_row_at(a, lc) * a.npad0 + 4 * kq, a.npad0 / 16, lc < m);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int p = kq + 4 * r, q = lc;
+            double v = g[r];
+            if (p >= m || q >= m) v = (p == q) ? 1.0 : 0.0;
+            if (p == q && v == 0.0) v = 1.0;
+            P[p][q] = v;
+        }
+    }
+    __syncthreads();
+    bool ok = true;
+    for (int j = 0; j < 16; ++j) ok = ok && isfinite(A[j][j]) && A[j][j] > 0.0;
+    inv_lower16(A, Li, tid);   // M[D, D]^-1
+    ok = chol16(P, tmp, tid) && ok;
+    if (tid == 0) {   // g = P[D, D]^-1 alpha[D]
+        for (int i = 0; i < 16; ++i) {
+            double s = i < m ? a.rows[(size_t)drop_row_at(a, i) * 4 + 3] : 0.0;
+            for (int k = 0; k < i; ++k) s = fma(-P[i][k], tmp[k], s);
+            tmp[i] = s / P[i][i];
+        }
+        for (int i = 15; i >= 0; --i) {
+            double s = tmp[i];
+            for (int k = i + 1; k < 16; ++k) s = fma(-P[k][i], gv[k], s);
+            gv[i] = s / P[i][i];
+        }
+        *a.flag = ok ? 1 : 0;
+    }
+    __syncthreads();
+    // u_i = (M[:, D] g)_i over the old rows, zero past n0
+    for (int i = tid; i < a.npad0; i += 256) {
+        double ws = 0.0;
+#pragma unroll
+        for (int b = 0; b < 16; ++b) {
+            const double v = (b < m && i < a.n0) ? a.src[(size_t)d[b] * a.npad0 + i] : 0.0;
+            ws = fma(v, gv[b], ws);
+        }
+        a.w[i] = ws;
+    }
+    // kept row c: V^T[.][c] = -(M[D, D]^-1)^T M[k_c, D]^T; zero past n2
+    for (int c = tid; c < a.npad1; c += 256) {
+        const int i = c < n2 ? drop_kept_row(d, m, c) : 0;
+        double col[16];
+#pragma unroll
+        for (int b = 0; b < 16; ++b) col[b] = (b < m && c < n2) ? a.src[(size_t)d[b] * a.npad0 + i] : 0.0;
+#pragma unroll
+        for (int p = 0; p < 16; ++p) {
+            double s = 0.0;
+#pragma unroll
+            for (int b = p; b < 16; ++b) s = fma(Li[b][p], col[b], s);
+            a.vt[(size_t)p * a.ldv + c] = p < m ? -s : 0.0;
+        }
+    }
+}
+
+// gp_drop_apply_kernel through the row set.  Column tile J holds the kept rows c = 16J .. 16J + 15 (old rows k_c):
+//   B_T[i][c] = src[k_c][k_i] + sum_b V[i][b] src[k_c][d_b],  M'_T = D_T (B_T - E_T S),  S += V_T^T B_T
+__global__ __launch_bounds__(64 * kDropWaves) void gp_drop_rows_apply_kernel(GPDrop a) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int J = blockIdx.x * kDropWaves + wave;
+    const int nt = a.npad1 / 16;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {   // the call's status so far and this block's
+        const int v = (*a.acc != 0 && *a.flag != 0) ? 1 : 0;
+        *a.acc = v;
+        if (a.ok) *a.ok = v;
+    }
+    if (J >= nt) return;   // wave-uniform
+    const int lc = lane & 15, kq = lane >> 4;
+    const int m = a.m, n2 = a.n0 - a.m;
+    int d[16];
+    drop_rows_load(a, d);
+    const int c = 16 * J + lc;
+    const bool cok = c < n2;
+    const int kc = cok ? drop_kept_row(d, m, c) : 0;
+    double* drow = a.dst + (size_t)c * a.npad1;
+    for (int T = 0; T < J; ++T)   // above the diagonal
+#pragma unroll
+        for (int r = 0; r < 4; ++r) drow[16 * T + kq + 4 * r] = 0.0;
+    const double* srow = a.src + (size_t)kc * a.npad0;
+    const double* varow = a.vt + (size_t)lc * a.ldv;
+    // M[D, k_c] in the B operand's layout (row b = kq + 4s), and its part of linvT[k_c] . u
+    f64x4 md;
+    double da = 0.0;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int b = kq + 4 * s, db = drop_row_at(a, b);
+        md[s] = (cok && b < m) ? srow[db] : 0.0;
+        da = fma(md[s], a.w[db], da);
+    }
+    f64x4 S = {0.0, 0.0, 0.0, 0.0};
+    for (int T = J; T < nt; ++T) {
+        const int i0 = 16 * T + kq;   // this lane's kept rows i0 + 4s
+        const double* et = a.et + (size_t)T * 256 + lc * 16 + kq;
+        const double* dt = a.dt + (size_t)T * 256 + lc * 16 + kq;
+        f64x4 bt, va, vb, ea, dd;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int i = i0 + 4 * s;
+            const int ki = i < n2 ? drop_kept_row(d, m, i) : 0;
+            bt[s] = (cok && i < n2) ? srow[ki] : 0.0;              // M[k_i][k_c]
+            va[s] = varow[i];                                      // V^T[lc][i]
+            vb[s] = a.vt[(size_t)(kq + 4 * s) * a.ldv + 16 * T + lc];   // V[16T + lc][kq + 4s]
+            ea[s] = et[4 * s];                                     // E_T[lc][kq + 4s]
+            dd[s] = dt[4 * s];                                     // D_T[lc][kq + 4s]
+            da = fma(bt[s], a.w[ki], da);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) bt = __builtin_amdgcn_mfma_f64_16x16x4f64(vb[s], md[s], bt, 0, 0, 0);
+        f64x4 y = bt;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) y = __builtin_amdgcn_mfma_f64_16x16x4f64(-ea[s], S[s], y, 0, 0, 0);
+        f64x4 o = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) o = __builtin_amdgcn_mfma_f64_16x16x4f64(dd[s], y[s], o, 0, 0, 0);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) S = __builtin_amdgcn_mfma_f64_16x16x4f64(va[s], bt[s], S, 0, 0, 0);
+        // o[r] = M'[i0 + 4r][c]; exact zeros above the diagonal and in the padding
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = i0 + 4 * r;
+            drow[i] = (cok && i < n2 && i >= c) ? o[r] : 0.0;
+        }
+    }
+    da += __shfl_xor(da, 16);
+    da += __shfl_xor(da, 32);
+    if (kq == 0) {   // kept row c: its weight, its inputs and its tile-pack entries, staged
+        const double4 zero = {0.0, 0.0, 0.0, 0.0};
+        const double4 rw = cok ? reinterpret_cast<const double4*>(a.rows)[kc] : zero;
+        const double4 tx = cok ? reinterpret_cast<const double4*>(a.tX)[kc] : zero;
+        const double al = cok ? rw.w - da : 0.0;
+        reinterpret_cast<double4*>(a.srows)[c] = double4{rw.x, rw.y, rw.z, al};
+        reinterpret_cast<double4*>(a.stX)[c] = tx;
+        double xc[3];
+        tile_centre(xc, rw.x, rw.y, rw.z, a.xbar, a.d);
+        tile_write_w(a.stW, tile_slot(J, lc), al, xc, cok);
+    }
+}
+
 hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream) {
     if (a.m < 1 || a.m > 16 || a.m >= a.n0 || a.npad0 % 16 != 0 || a.npad1 % 16 != 0 || a.n0 > a.npad0 ||
         a.n0 - a.m > a.npad1 || a.npad1 > a.npad0 || a.ldv < a.npad1)
         return hipErrorInvalidValue;
     const int nt = a.npad1 / 16;
+    if (a.didx != nullptr) {
+        if (a.acc == nullptr || a.ldv < a.npad0) return hipErrorInvalidValue;
+        GP_LAUNCH(gp_drop_rows_head_kernel, dim3(1), dim3(256), stream, a);
+        GP_LAUNCH(gp_drop_tile_kernel, dim3(nt), dim3(64), stream, a);
+        GP_LAUNCH(gp_drop_rows_apply_kernel, dim3((nt + kDropWaves - 1) / kDropWaves), dim3(64 * kDropWaves), stream, a);
+        return hipSuccess;
+    }
     GP_LAUNCH(gp_drop_head_kernel, dim3(1), dim3(256), stream, a);
     GP_LAUNCH(gp_drop_tile_kernel, dim3(nt), dim3(64), stream, a);
     GP_LAUNCH(gp_drop_apply_kernel, dim3((nt + kDropWaves - 1) / kDropWaves), dim3(64 * kDropWaves), stream, a);
+    return hipSuccess;
+}
+
+hipError_t launch_gp_drop_prep(const GPDropPrep& a, hipStream_t stream) {
+    if (a.m < 1 || a.m >= a.n || !a.idx || !a.mask || !a.sorted || !a.acc) return hipErrorInvalidValue;
+    GP_LAUNCH(gp_drop_prep_kernel, dim3(1), dim3(256), stream, a);
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------- the rows missed least (gpmpc_gp_redundant)
+// Deleting row j turns the precision P = M^T M into P[k, k] - P[k, j] P[j, k] / P_jj, and 1 / P_ii - sn2 is row i's
+// latent leave-one-out variance: what the other rows still say about x_i.  Greedy backward selection is therefore a
+// pivoted partial Cholesky of P, the mirror of gpmpc_gp_select: with P_ij = linvT[i] . linvT[j],
+//   c_t[i] = (P_ij - sum_{s<t} c_s[i] c_s[j]) / sqrt(p_j),  p_i -= c_t[i]^2,
+// the pick being the row whose score max_g (1 / p_g,i - sn2_g) / sf2_g is smallest.  A row inert in GP g (a zero on
+// the diagonal of M) has a zero row of linvT: its term is 0 and g is not conditioned on it.
+// One launch per pick, no grid-wide barrier: every workgroup reduces the previous launch's per-block bests to the
+// same j_t, conditions its kRedundantBlock rows and leaves its own best for the next launch; p and the bests are
+// double-buffered by the parity of t.  A workgroup is kRedundantBlock rows times kRedParts parts of the inner
+// product: part q takes the column tiles [q nt / 16, (q + 1) nt / 16) of the two rows and the c columns
+// s = q, q + 16, .., one sequential sum, and the parts are added as a balanced tree.  No atomics.
+constexpr int kRedParts = 16;
+constexpr int kRedThreads = kRedundantBlock * kRedParts;
+constexpr int kRedNone = 0x7fffffff;
+struct RedBest {
+    double val;
+    int idx, nf;   // the smallest finite score's row (kRedNone: none); the lowest row with a non-finite score
+};
+__device__ __forceinline__ RedBest red_merge(const RedBest& x, const RedBest& y) {
+    RedBest r = x;
+    if (y.idx != kRedNone && (x.idx == kRedNone || y.val < x.val || (y.val == x.val && y.idx < x.idx))) {
+        r.val = y.val;
+        r.idx = y.idx;
+    }
+    r.nf = min(x.nf, y.nf);
+    return r;
+}
+__device__ __forceinline__ RedBest red_candidate(double s, int i, bool open) {
+    const bool fin = isfinite(s);
+    return RedBest{(open && fin) ? s : 0.0, (open && fin) ? i : kRedNone, (open && !fin) ? i : kRedNone};
+}
+// over each group of kRedundantBlock consecutive lanes; the group's first lane holds the result
+__device__ __forceinline__ RedBest red_group_best(RedBest b) {
+#pragma unroll
+    for (int off = kRedundantBlock / 2; off >= 1; off >>= 1) {
+        RedBest o;
+        o.val = __shfl_down(b.val, off, kRedundantBlock);
+        o.idx = __shfl_down(b.idx, off, kRedundantBlock);
+        o.nf = __shfl_down(b.nf, off, kRedundantBlock);
+        b = red_merge(b, o);
+    }
+    return b;
+}
+// Part kp of linvT[i] . linvT[j] (whole tiles: rows are 128-byte aligned)
+__device__ __forceinline__ double red_dot_part(const GPRedundantGP& g, int i, int j, int kp) {
+    const int nt = g.npad / 16;
+    const int q0 = 4 * (kp * nt / kRedParts), q1 = 4 * ((kp + 1) * nt / kRedParts);
+    const double4* ri = reinterpret_cast<const double4*>(g.linvT + (size_t)i * g.npad);
+    const double4* rj = reinterpret_cast<const double4*>(g.linvT + (size_t)j * g.npad);
+    double acc = 0.0;
+    for (int q = q0; q < q1; ++q) {
+        const double4 x = ri[q], y = rj[q];
+        acc = fma(x.x, y.x, acc);
+        acc = fma(x.y, y.y, acc);
+        acc = fma(x.z, y.z, acc);
+        acc = fma(x.w, y.w, acc);
+    }
+    return acc;
+}
+// the parts of one row, ((0 + 1) + (2 + 3)) + ..
+__device__ __forceinline__ double red_tree(const double (*part)[kRedundantBlock], int ci) {
+    double r[kRedParts];
+#pragma unroll
+    for (int q = 0; q < kRedParts; ++q) r[q] = part[q][ci];
+#pragma unroll
+    for (int w = kRedParts / 2; w >= 1; w >>= 1)
+#pragma unroll
+        for (int q = 0; q < w; ++q) r[q] = r[2 * q] + r[2 * q + 1];
+    return r[0];
+}
+__device__ __forceinline__ bool red_live(const GPRedundantGP& g, int i) { return g.linvT[(size_t)i * g.npad + i] != 0.0; }
+// GP g's term of row i's score, folded into the largest so far (a NaN stays: nothing compares above it)
+__device__ __forceinline__ double red_score(const GPRedundantGP& g, int gi, bool live, double p, double s) {
+    const double t = live ? (1.0 / p - g.sn2) / g.sf2 : 0.0;
+    return (gi == 0 || t > s || t != t) ? t : s;
+}
+
+// The start state: p_g,i = |linvT_g[i]|^2, nothing picked, each block's best, ok = 1
+__global__ __launch_bounds__(kRedThreads) void gp_redundant_init_kernel(const GPRedundant a) {
+    __shared__ double part[kRedParts][kRedundantBlock];
+    const int tid = threadIdx.x;
+    const int ci = tid % kRedundantBlock, kp = tid / kRedundantBlock;
+    const int i = blockIdx.x * kRedundantBlock + ci;
+    const bool valid = i < a.n;
+    const int ii = valid ? i : a.n - 1;
+    double score = 0.0;
+    for (int gi = 0; gi < a.n_gp; ++gi) {
+        const GPRedundantGP& g = a.g[gi];
+        part[kp][ci] = red_dot_part(g, ii, ii, kp);
+        __syncthreads();
+        if (kp == 0 && valid) {
+            const double p = red_tree(part, ci);
+            a.p[(size_t)gi * a.ldn + i] = p;
+            score = red_score(g, gi, red_live(g, i), p, score);
+        }
+        __syncthreads();
+    }
+    if (kp == 0) {
+        RedBest nb{0.0, kRedNone, kRedNone};
+        if (valid) {
+            a.state[i] = 0;
+            nb = red_candidate(score, i, true);
+        }
+        nb = red_group_best(nb);
+        if (tid == 0) {
+            a.bval[blockIdx.x] = nb.val;
+            a.bidx[2 * blockIdx.x] = nb.idx;
+            a.bidx[2 * blockIdx.x + 1] = nb.nf;
+        }
+    }
+    if (blockIdx.x == 0 && tid == 0 && a.ok != nullptr) a.ok[0] = 1;
+}
+
+// Pick t
+__global__ __launch_bounds__(kRedThreads) void gp_redundant_step_kernel(const GPRedundant a, const int t) {
+    __shared__ double sval[kRedThreads];
+    __shared__ int sidx[kRedThreads], snf[kRedThreads];
+    __shared__ double part[kRedParts][kRedundantBlock];
+    const int tid = threadIdx.x;
+    const int cur = t & 1, nxt = cur ^ 1;
+    RedBest b{0.0, kRedNone, kRedNone};
+    for (int k = tid; k < a.nblk; k += kRedThreads) {
+        const size_t at = (size_t)cur * a.nblk + k;
+        b = red_merge(b, RedBest{a.bval[at], a.bidx[2 * at], a.bidx[2 * at + 1]});
+    }
+    sval[tid] = b.val;
+    sidx[tid] = b.idx;
+    snf[tid] = b.nf;
+    __syncthreads();
+    for (int s = kRedThreads / 2; s >= 1; s >>= 1) {
+        if (tid < s) {
+            const RedBest r = red_merge(RedBest{sval[tid], sidx[tid], snf[tid]},
+                                        RedBest{sval[tid + s], sidx[tid + s], snf[tid + s]});
+            sval[tid] = r.val;
+            sidx[tid] = r.idx;
+            snf[tid] = r.nf;
+        }
+        __syncthreads();
+    }
+    const bool fin = sidx[0] != kRedNone;   // a finite score is left; else the non-finite ones in index order
+    const int j = fin ? sidx[0] : snf[0];
+    const double sj = sval[0];
+    if (j < 0 || j >= a.n) return;   // (m < n leaves a row for every pick; uniform)
+    if (blockIdx.x == 0 && tid == 0) {
+        a.pick[t] = j;
+        if (a.score != nullptr) a.score[t] = fin ? sj : __longlong_as_double(0x7ff8000000000000ll);
+    }
+    const int ci = tid % kRedundantBlock, kp = tid / kRedundantBlock;
+    const int i = blockIdx.x * kRedundantBlock + ci;
+    const bool valid = i < a.n;
+    const int ii = valid ? i : a.n - 1;
+    const size_t ldn = a.ldn;
+    double score = 0.0;
+    for (int gi = 0; gi < a.n_gp; ++gi) {
+        const GPRedundantGP& g = a.g[gi];
+        const double* pin = a.p + ((size_t)cur * a.n_gp + gi) * ldn;
+        double* pout = a.p + ((size_t)nxt * a.n_gp + gi) * ldn;
+        const double pj = pin[j];
+        const bool livej = red_live(g, j);
+        const bool good = livej && isfinite(pj) && pj > 0.0;   // (uniform over the workgroup)
+        if (livej && !good && blockIdx.x == 0 && tid == 0 && a.ok != nullptr) a.ok[0] = 0;
+        double cv = 0.0;
+        if (good) {
+            double acc = red_dot_part(g, ii, j, kp);
+            for (int s = kp; s < t; s += kRedParts) acc = fma(-g.ccol[(size_t)s * ldn + ii], g.ccol[(size_t)s * ldn + j], acc);
+            part[kp][ci] = acc;
+            __syncthreads();
+            if (kp == 0) cv = red_tree(part, ci) / sqrt(pj);
+            __syncthreads();
+        }
+        if (kp == 0 && valid) {
+            g.ccol[(size_t)t * ldn + i] = cv;
+            const double pn = pin[i] - cv * cv;
+            pout[i] = pn;
+            score = red_score(g, gi, red_live(g, i), pn, score);
+        }
+    }
+    if (kp == 0) {   // (the first kRedundantBlock lanes of wave 0)
+        RedBest nb{0.0, kRedNone, kRedNone};
+        if (valid) {
+            int st = a.state[i];
+            if (i == j) a.state[i] = st = 1;
+            nb = red_candidate(score, i, st == 0);
+        }
+        nb = red_group_best(nb);
+        if (tid == 0) {
+            const size_t at = (size_t)nxt * a.nblk + blockIdx.x;
+            a.bval[at] = nb.val;
+            a.bidx[2 * at] = nb.idx;
+            a.bidx[2 * at + 1] = nb.nf;
+        }
+    }
+}
+
+hipError_t launch_gp_redundant(const GPRedundant& a, hipStream_t stream) {
+    if (a.n < 2 || a.m < 1 || a.m >= a.n || a.m > kRedundantMaxPicks || a.n > a.ldn || a.n_gp < 1 || a.n_gp > kMaxGP ||
+        a.nblk != (a.n + kRedundantBlock - 1) / kRedundantBlock)
+        return hipErrorInvalidValue;
+    for (int g = 0; g < a.n_gp; ++g)
+        if (a.g[g].npad < 16 || a.g[g].npad % 16 != 0 || a.n > a.g[g].npad) return hipErrorInvalidValue;
+    GP_LAUNCH(gp_redundant_init_kernel, dim3(a.nblk), dim3(kRedThreads), stream, a);
+    for (int t = 0; t < a.m; ++t) GP_LAUNCH(gp_redundant_step_kernel, dim3(a.nblk), dim3(kRedThreads), stream, a, t);
     return hipSuccess;
 }
 

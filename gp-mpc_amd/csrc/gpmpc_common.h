@@ -325,6 +325,46 @@ struct GPDrop {
     double* dt;
     int32_t* flag;
     int32_t* ok;          // the caller's status word of this block, may be null
+    // gpmpc_gp_drop_rows only (null: the m oldest rows).  didx: the block's m rows, ascending, indices into the rows
+    // before the block (device); w then holds M[:, D] g over all npad0 old rows.  acc: the call's running status
+    // (gp_drop_prep_kernel starts it); ok then receives acc & flag, one word for the whole call.
+    const int32_t* didx;
+    int32_t* acc;
+};
+
+// The row set of gpmpc_gp_drop_rows (gp_drop.hip), made ascending on the device: the distinct indices of idx within
+// 0 .. n-1, filled up to m with the lowest rows not among them.  acc = 1 when idx held m distinct indices in range.
+struct GPDropPrep {
+    const int32_t* idx;   // [m] the caller's indices (device)
+    int32_t n, m;         // 1 <= m < n
+    int32_t* mask;        // [n] scratch
+    int32_t* sorted;      // [m] the rows dropped, ascending
+    int32_t* dropped;     // [m] the caller's copy, may be null
+    int32_t* acc;
+};
+
+// Greedy backward selection of the m rows the GPs would miss least (gp_drop.hip; gpmpc_gp_redundant fills it): a
+// pivoted partial Cholesky of the precisions P_g = M_g^T M_g, whose entries are inner products of rows of linvT.
+constexpr int kRedundantMaxPicks = 256;
+constexpr int kRedundantBlock = 16;   // rows per workgroup of the pick loop
+struct GPRedundantGP {
+    const double* linvT;  // [npad][npad]
+    double* ccol;         // [m][ldn]: c_t[i]
+    int32_t npad;
+    double sf2, sn2;
+};
+struct GPRedundant {
+    int32_t n, m, n_gp;
+    int32_t ldn;          // stride of the per-row arrays (>= n)
+    int32_t nblk;         // ceil(n / kRedundantBlock)
+    GPRedundantGP g[kMaxGP];
+    double* p;            // [2][n_gp][ldn]: step t reads half t & 1 and writes the other
+    int32_t* state;       // [ldn]: 1 picked
+    double* bval;         // [2][nblk]: each block's smallest finite score among its unpicked rows
+    int32_t* bidx;        // [2][nblk][2]: its index (INT_MAX: none), the block's lowest unpicked row with a non-finite score
+    int32_t* pick;        // [m]
+    double* score;        // [m] or null
+    int32_t* ok;          // [1] or null
 };
 
 // A from-scratch factorisation of an exact GP from its device-resident rows (gp_refactor.hip;
@@ -519,6 +559,9 @@ struct GPSelect {
 hipError_t launch_gp_select(const GPSelect& a, hipStream_t stream);
 hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream);
 hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream);
+hipError_t launch_gp_drop_prep(const GPDropPrep& a, hipStream_t stream);
+// the start values and bests, then one launch per pick
+hipError_t launch_gp_redundant(const GPRedundant& a, hipStream_t stream);
 hipError_t launch_gp_refactor(const GPRefactor& a, hipStream_t stream);
 // Its pieces, which the fit's iterations queue around a Khat built from device-resident hyperparameters:
 // the status word set to 1 and the inert mask / masked targets; the 2 nt panel and update launches on a

@@ -40,6 +40,7 @@ SIGNATURES = {
     "gpmpc_gp_reserve": (_I, [_P, _I, _I]),
     "gpmpc_gp_append": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "gpmpc_gp_drop_oldest": (_I, [_P, _I, _I, _P, _P]),
+    "gpmpc_gp_drop_rows": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "gpmpc_gp_refactor": (_I, [_P, _I, _P, _D, _D, _D, _P, _P]),
     "gpmpc_gp_mll": (_I, [_P, _I, _P, _P, _P]),
     "gpmpc_gp_fit": (_I, [_P, _I, _P, _D, _I, POINTER(_D), POINTER(_I), POINTER(_I), _P, _P]),
@@ -63,6 +64,7 @@ SIGNATURES = {
     "gpmpc_preprocess": (_I, [_P, _I, _P, _P, _P, _I, _P, _D, _D, _P, _P, _P]),
     "gpmpc_gp_informative": (_I, [_P, _I, _P, _P, _I, _P, _P, _P]),
     "gpmpc_gp_select": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "gpmpc_gp_redundant": (_I, [_P, _I, _P, _P, _P, _P]),
     "gpmpc_gp_observe": (_I, [_P, _I, _P, _P, _P, _I, _P, _D, _D, _I, _P, _P, _P, _P, _P]),
     "gpmpc_set_launch": (_I, [_P, _I]),
     "gpmpc_set_profiling": (_I, [_P, _I]),

@@ -120,6 +120,26 @@ class GaussianProcess:
         self.K, self.K_inv, self._dev = None, None, None
         return self
 
+    def drop_rows(self, idx):
+        """Remove the training rows ``idx`` names (m distinct indices in 0 .. n-1, 1 <= m < n; a host or device
+        tensor or an array), the kept rows keeping their order, hyperparameters unchanged: the mirror of
+        ``BatchSolver.drop_rows``, which reports the rows it dropped as a device tensor.  No index is read on the
+        host: the kept count n - m is known, so a stable sort of the membership mask gives the kept rows.  The
+        cached covariances and device layout are dropped."""
+        X = self.train_inputs[0]
+        idx = torch.as_tensor(idx).to(X.device, torch.int64).reshape(-1)
+        m, n = int(idx.shape[0]), self.n_ind_points
+        if not 1 <= m < n:
+            raise ValueError(f"drop_rows: the number of rows must be 1..{n - 1} (at least one row stays), got {m}")
+        mask = torch.zeros(n, dtype=torch.int8, device=X.device)
+        mask[idx] = 1
+        keep = torch.sort(mask, stable=True).indices[:n - m]
+        self.train_inputs = (X[keep].clone(),)
+        self.train_targets = self.train_targets[keep].clone()
+        self.n_ind_points = n - m
+        self.K, self.K_inv, self._dev = None, None, None
+        return self
+
     def parameters(self):
         return [self.raw_lengthscale, self.raw_outputscale, self.raw_noise]
 

@@ -276,6 +276,33 @@ class GPMPC:
             self.gaussian_process[i].drop_oldest(m)
         return flags
 
+    def drop_rows(self, idx) -> list[torch.Tensor]:
+        """Remove the training rows ``idx`` names (distinct int32 indices into the current rows; a device or host
+        tensor or an array) of every GP on the solver handle, on the device (``BatchSolver.drop_rows``, queued on
+        the current stream, no refactorisation), and of the Python GP objects with them
+        (``GaussianProcess.drop_rows``, from the rows the handle reports as dropped, so no index is read on the
+        host): the mirror of ``drop_oldest`` for an arbitrary set, such as an outlier or the picks of
+        ``BatchSolver.redundant``.  At least one row stays.  Returns the status flags per GP (device tensors [1]; a
+        0 means the indices were not distinct values in range, or that GP must be uploaded again).  Sparse mode,
+        LOVE roots and FITC means as for ``drop_oldest``."""
+        if self.sparse and self.fitc != "device":
+            raise _lib.GPMPCError("drop_rows: not available in sparse (FITC) mode")
+        assert self.gaussian_process is not None and not self._requires_recompile, \
+            "GP model must be uploaded (call reset())"
+        idx = torch.as_tensor(idx).to(self.device, torch.int32).reshape(-1)
+        m, n = int(idx.shape[0]), self.solver.gp_size(0)[0]
+        if not 1 <= m < n:   # before any GP changes, so the handle's GPs stay in step
+            raise ValueError(f"drop_rows: the number of rows must be 1..{n - 1} (at least one row stays), got {m}")
+        return self._update_gps(lambda: self._drop_rows(idx))
+
+    def _drop_rows(self, idx: torch.Tensor) -> list[torch.Tensor]:
+        flags = []
+        for i in range(len(self.gp_idx)):
+            dropped, ok = self.solver.drop_rows(i, idx)
+            self.gaussian_process[i].drop_rows(dropped)
+            flags.append(ok)
+        return flags
+
     def append_data(self, inputs: np.ndarray, targets: np.ndarray, evict_oldest: bool = False) -> list[torch.Tensor]:
         """Fold new observations into the uploaded GPs between two control steps, hyperparameters
         unchanged: ``inputs`` (m, sum d_g) and ``targets`` (m, n_gp) in GP-input space, as
@@ -322,7 +349,7 @@ class GPMPC:
         return self._update_gps(update)
 
     def observe(self, x, u, x_next, pick=None, m: int | None = None, select: str | None = None,
-                evict_oldest: bool = False):
+                evict_oldest: bool = False, evict: str | None = None):
         """``preprocess_data`` followed by ``append_data`` without leaving the device: transitions x (P, nx),
         u (P, nu), x_next (P, nx) (device tensors as ``select_action_batch`` and ``plant_step`` produce them, or
         host arrays) become GP training rows on the device and are appended to every GP of the solver handle
@@ -336,13 +363,23 @@ class GPMPC:
         chosen one after the other, each the least certain once the ones before it count as observed
         (``BatchSolver.select``), so a step's near-duplicates are not all taken.  ``evict_oldest``, the capacity check, the
         LOVE roots, the device-built FITC means and the refusals in sparse mode are ``append_data``'s.  Returns
-        ``(inputs, targets, accepted, dropped_ok)`` as ``BatchSolver.observe`` does."""
+        ``(inputs, targets, accepted, dropped_ok)`` as ``BatchSolver.observe`` does.
+
+        ``evict="redundant"`` (instead of ``evict_oldest``; passing both is an error) chooses what leaves a full
+        window: when the new rows would exceed the capacity, the excess (at most 256 rows) is the rows the GPs would
+        miss least (``BatchSolver.redundant``), removed from every GP of the handle and from the Python GP objects
+        (``drop_rows``) before the append, which then evicts nothing.  The eviction is decided before the new rows
+        are seen.  ``dropped_ok`` then holds the (n_gp, 1) flags of ``BatchSolver.drop_rows``."""
         if self.sparse and self.fitc != "device":
             raise _lib.GPMPCError("observe: not available in sparse (FITC) mode")
         assert self.gaussian_process is not None and not self._requires_recompile, \
             "GP model must be uploaded (call reset())"
         if select not in (None, "variance", "greedy"):
             raise ValueError("select must be None, 'variance' or 'greedy'")
+        if evict not in (None, "redundant"):
+            raise ValueError("evict must be None or 'redundant'")
+        if evict is not None and evict_oldest:
+            raise ValueError("evict_oldest and evict both say what leaves a full window: pass one of them")
         s = self.solver
         x, u, x_next = s._transitions(x, u, x_next)
         if select is not None:
@@ -354,19 +391,24 @@ class GPMPC:
         n, cap = s.gp_size(0)
         excess = n + rows - cap
         # before any GP changes, so the handle's GPs stay in step (an eviction leaves at least one old row)
-        if excess > 0 and (not evict_oldest or excess >= n):
+        if excess > 0 and (not (evict_oldest or evict) or excess >= n):
             raise _lib.GPMPCError(f"observe: capacity exceeded ({n} + {rows} rows, capacity {cap}; "
                                   "construct GPMPC with gp_capacity)")
+        if excess > 256 and evict == "redundant":
+            raise ValueError(f"evict='redundant' chooses at most 256 rows per call, {excess} would have to leave")
 
         def update():
             p = s.informative(x, u, rows) if select == "variance" else s.select(x, u, rows)[0] if select == "greedy" else pick
+            flags = None
+            if excess > 0 and evict == "redundant":   # (decided on the GPs as they are: before the new rows are seen)
+                flags = torch.stack(self._drop_rows(s.redundant(excess)))
             out = s.observe(x, u, x_next, pick=p, m=rows, evict_oldest=evict_oldest)
             inputs, targets = out[0], out[1]
             for i, idx in enumerate(self.gp_idx):
-                if excess > 0:
+                if excess > 0 and flags is None:
                     self.gaussian_process[i].drop_oldest(excess)
                 self.gaussian_process[i].append_data(inputs[:, idx], targets[:, i])
-            return out
+            return out if flags is None else (out[0], out[1], out[2], flags)
 
         return self._update_gps(update)
 

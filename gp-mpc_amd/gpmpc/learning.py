@@ -61,7 +61,7 @@ def run_evaluation(ctrl, x0: np.ndarray, steps: int, tstep0: np.ndarray | None =
 
 def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, seed: int,
                        tstep0: np.ndarray | None = None, sliding: bool = False, refresh_every: int = 0,
-                       device_data: bool = False, select: str = "random") -> dict:
+                       device_data: bool = False, select: str = "random", evict: str | None = None) -> dict:
     """A closed-loop episode that learns while it runs: after every plant step a seeded random
     choice of ``append_per_step`` of the step's B transitions is preprocessed
     (``GPMPC.preprocess_data``) and appended to the uploaded GPs (``GPMPC.append_data``, a
@@ -81,14 +81,23 @@ def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, s
     (``BatchSolver.informative``) and uploads nothing; ``select="greedy"`` (likewise) picks them one after the other,
     each conditioned on the ones before it (``BatchSolver.select``).  The two paths differ by rounding in the targets.
 
+    ``evict="redundant"`` (needs ``device_data=True, sliding=True``) chooses what leaves the full window as well: the
+    rows the GPs would miss least (``GPMPC.observe(evict="redundant")``, ``BatchSolver.redundant``) instead of the
+    oldest.
+
     Returns the dict of :func:`run_evaluation` plus ``n_train`` (steps,), the training rows after
     each step; with ``device_data=True`` also ``pick``, the list of every step's picked indices."""
     if select not in ("random", "variance", "greedy"):
         raise ValueError("select must be 'random', 'variance' or 'greedy'")
     if select != "random" and not device_data:
         raise ValueError(f"select='{select}' picks on the device: it needs device_data=True")
+    if evict not in (None, "redundant"):
+        raise ValueError("evict must be None or 'redundant'")
+    if evict is not None and not (device_data and sliding):
+        raise ValueError(f"evict='{evict}' chooses the rows that leave on the device: it needs device_data=True, sliding=True")
     if device_data:
-        return _run_online_episode_device(ctrl, x0, steps, append_per_step, seed, tstep0, sliding, refresh_every, select)
+        return _run_online_episode_device(ctrl, x0, steps, append_per_step, seed, tstep0, sliding, refresh_every, select,
+                                          evict)
     ctrl.reset()
     solver = ctrl.solver
     dev = solver.device
@@ -121,9 +130,12 @@ def run_online_episode(ctrl, x0: np.ndarray, steps: int, append_per_step: int, s
     return {k: np.array(v) for k, v in data.items()}
 
 
-def _run_online_episode_device(ctrl, x0, steps, append_per_step, seed, tstep0, sliding, refresh_every, select) -> dict:
+def _run_online_episode_device(ctrl, x0, steps, append_per_step, seed, tstep0, sliding, refresh_every, select,
+                               evict=None) -> dict:
     """:func:`run_online_episode` with ``device_data=True``: the same loop on device tensors."""
     ctrl.reset()
+    # what makes room in a full window: the oldest rows, or the rows evict names
+    room_for = dict(evict=evict) if evict is not None else dict(evict_oldest=sliding)
     solver = ctrl.solver
     dev = solver.device
     B = solver.batch
@@ -151,7 +163,7 @@ def _run_online_episode_device(ctrl, x0, steps, append_per_step, seed, tstep0, s
                 pick = pick[:room]
             if len(pick):
                 pick = torch.as_tensor(pick.astype(np.int32)).to(dev)
-                ctrl.observe(obs[step], action[step], obs[step + 1], pick=pick, evict_oldest=sliding)
+                ctrl.observe(obs[step], action[step], obs[step + 1], pick=pick, **room_for)
             picks.append(pick)
         else:
             m = min(append_per_step, B) if sliding else min(append_per_step, B, room)
@@ -160,7 +172,7 @@ def _run_online_episode_device(ctrl, x0, steps, append_per_step, seed, tstep0, s
                 # (the indices are read back after the episode; the rows they name are the appended inputs)
                 pick = (solver.informative(obs[step], action[step], m) if select == "variance"
                         else solver.select(obs[step], action[step], m)[0])
-                ctrl.observe(obs[step], action[step], obs[step + 1], pick=pick, evict_oldest=sliding)
+                ctrl.observe(obs[step], action[step], obs[step + 1], pick=pick, **room_for)
             picks.append(pick)
         if refresh_every > 0 and (step + 1) % refresh_every == 0:
             ctrl.refresh_gps()

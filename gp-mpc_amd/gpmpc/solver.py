@@ -208,6 +208,39 @@ class BatchSolver:
         _lib.check(self.lib.gpmpc_gp_drop_oldest(self._h, int(gp_id), m, flags.data_ptr(), self._stream()))
         return flags
 
+    def drop_rows(self, gp_id: int, idx) -> tuple[torch.Tensor, torch.Tensor]:
+        """Remove the training rows ``idx`` names (int32 indices into the rows as they are now; a cuda or host
+        tensor or an array) of the handle's GP ``gp_id`` on the current stream (gpmpc_gp_drop_rows): ``drop_gp`` for
+        an arbitrary set, the kept rows keeping their order; no refactorisation and no synchronisation of its own.
+        Needs ``reserve_gp`` and leaves at least one row.  Returns ``(dropped, ok)``, device int32 tensors: the rows
+        actually dropped, ascending (m,), and the flag [1], 1 when the indices were distinct values in range and
+        every pivot was finite and positive.  Indices that are not come out as the distinct ones in range, filled
+        up with the lowest rows not among them, and ok 0 with the GP valid; after a 0 caused by a pivot the GP's
+        contents are unspecified, upload it again.  The Python GP objects are not touched
+        (``GaussianProcess.drop_rows``)."""
+        idx = torch.as_tensor(idx).to(self.device, torch.int32).reshape(-1).contiguous()
+        m = int(idx.shape[0])
+        dropped = torch.empty(max(m, 1), dtype=torch.int32, device=self.device)
+        ok = torch.empty(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.gpmpc_gp_drop_rows(self._h, int(gp_id), m, idx.data_ptr() if m else None,
+                                               dropped.data_ptr(), ok.data_ptr(), self._stream()))
+        return dropped[:m], ok
+
+    def redundant(self, m: int, scores: bool = False):
+        """The ``m`` <= 256 training rows the handle's GPs would miss least (gpmpc_gp_redundant), one after the
+        other: each pick is the row whose latent leave-one-out variance, the largest over the GPs divided by the
+        outputscale, is smallest once the picks before it are gone, so of a cluster of near-copies all but one
+        leave before a row that covers a region alone.  Ties go to the lower (older) index.  Returns the device
+        int32 picks (m,), with ``scores=True`` also the (m,) scores at which they were picked and the int32 flag
+        tensor [1] (0: a pivot was not finite and positive, and that GP skipped that pick).  On the current
+        stream, no synchronisation of its own; nothing of the GPs changes."""
+        m = int(m)
+        pick = torch.empty(max(m, 1), dtype=torch.int32, device=self.device)   # (never empty: the refusal is the library's)
+        score = torch.empty(max(m, 1), dtype=torch.float64, device=self.device) if scores else None
+        ok = torch.empty(1, dtype=torch.int32, device=self.device) if scores else None
+        _lib.check(self.lib.gpmpc_gp_redundant(self._h, m, pick.data_ptr(), _lib.ptr(score), _lib.ptr(ok), self._stream()))
+        return (pick[:m], score[:m], ok) if scores else pick[:m]
+
     # ------------------------------------------------------------------ training data on the device
     def _diff_constants(self) -> tuple[float, float]:
         """(dt_diff, gravity) of ``GPMPC.preprocess_data``: the reference's literals 1/60 and 9.81 for quad3d

@@ -143,6 +143,26 @@ gpmpc_status gpmpc_gp_append(gpmpc_handle* h, int32_t gp_id, int32_t m, const do
  * gpmpc_gp_reserve since gpmpc_set_gp -- the update writes the factor into the second buffer a reserve allocates (GPMPC_ERR_STATE). */
 gpmpc_status gpmpc_gp_drop_oldest(gpmpc_handle* h, int32_t gp_id, int32_t m, int32_t* ok_dev, void* stream);
 
+/* Remove the m training rows idx_dev names (device int32 [m], indices into the rows as they are when the call is
+ * made) of GP gp_id on `stream`: gpmpc_gp_drop_oldest for an arbitrary set, to take out an outlier, a row whose
+ * target is no longer trusted, or the rows gpmpc_gp_redundant chose.  The kept rows keep their order; row counts,
+ * xbar, capacity and hyperparameters behave as after gpmpc_gp_drop_oldest, and the linearisation cache is invalidated.
+ * One launch sorts the set ascending into scratch of the GP; then blocks of up to 16 rows are taken from the highest
+ * indices down (so no block shifts the rows of the blocks after it), each a rank-m update of (L^-1)^T and alpha
+ * through the kept-row map (csrc/gp_drop.hip): no refactorisation, no host synchronisation, nothing read back.
+ * Indices that are not m distinct values in 0 .. n-1 cannot be refused without a read-back, so the call stays well
+ * defined: the rows dropped are the distinct indices in range, and while these are fewer than m the lowest rows not
+ * yet among them are added; ok_dev then reads 0 and the GP is valid.
+ * dropped_dev: device int32 [m], may be NULL; the rows actually dropped, ascending (the caller who keeps the
+ * targets needs it).  ok_dev: device int32 [1], may be NULL; 1 when the indices were m distinct values in range and
+ * every pivot of every block was finite and positive.  After a 0 caused by a pivot the contents of the GP are
+ * unspecified but every access stayed in bounds, as for gpmpc_gp_drop_oldest.  Inert rows may be among the dropped
+ * and the kept rows (a zero on the diagonal of M[D,D] / P[D,D] reads as 1); kept ones stay inert.
+ * Refused, with the GP unchanged: m < 1, m >= n or idx_dev NULL (GPMPC_ERR_ARG); what gpmpc_gp_drop_oldest refuses
+ * of the GP's state (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_gp_drop_rows(gpmpc_handle* h, int32_t gp_id, int32_t m, const int32_t* idx_dev,
+                                int32_t* dropped_dev, int32_t* ok_dev, void* stream);
+
 /* Factorise GP gp_id again from scratch on `stream`, from what the device already holds: the
  * handle's own training inputs, the caller's device targets y_dev [n] (float64, the targets of the
  * GP's n current rows in row order; n as gpmpc_gp_size reports it, inert rows included) and the
@@ -427,6 +447,32 @@ gpmpc_status gpmpc_gp_informative(gpmpc_handle* h, int32_t P, const double* x_de
  * Refused: as gpmpc_gp_informative, and m > 256 (GPMPC_ERR_ARG). */
 gpmpc_status gpmpc_gp_select(gpmpc_handle* h, int32_t P, const double* x_dev, const double* u_dev, int32_t m,
                              int32_t* pick_dev, double* gain_dev, double* resid_dev, int32_t* ok_dev, void* stream);
+
+/* The m training rows the handle's GPs would miss least, one after the other: greedy backward selection, the mirror
+ * of gpmpc_gp_select for the rows that leave a full window.  Every GP of the model must be set exactly with Linv, and
+ * all must hold the same n rows.  With M_g = L_g^-1 and the precision P_g = M_g^T M_g, 1 / P_g,ii - noise_g is row
+ * i's latent leave-one-out variance, what the other rows still say about x_i, and deleting row j turns P_g into
+ * P_g[k,k] - P_g[k,j] P_g[j,k] / P_g,jj: a pivoted partial Cholesky of P_g, whose entries are inner products of rows
+ * of (L_g^-1)^T.  Start from p_g,i = |linvT_g[i]|^2; a row inert in GP g has p = 0, its term below is 0 and it takes
+ * no part in g's conditioning.  Then for t = 0 .. m-1:
+ *   score    s_i = max_g (1 / p_g,i - noise_g) / outputscale_g over the rows not yet picked;
+ *   pick     j_t = the smallest score, ties to the lower index (the older row leaves first), a score that is not
+ *            finite after every finite one: pick_dev[t] = j_t, score_dev[t] = s_{j_t};
+ *   condition, every GP in which j is live: c_g,t[i] = (P_g,ij - sum_{s<t} c_g,s[i] c_g,s[j]) / sqrt(p_g,j),
+ *            p_g,i -= c_g,t[i]^2 for every i.  A p_g,j that is not finite and positive skips GP g for this pick and
+ *            clears ok_dev[0], which is otherwise written as 1.
+ * The score of the remaining rows never decreases from pick to pick.  pick_dev: device int32 [m]; score_dev (device
+ * float64 [m]) and ok_dev (device int32 [1]) may be NULL.  Every output is fixed bit for bit by the inputs: each
+ * inner product is split over 16 parts of fixed extent added as a balanced tree, no atomics.  A LOVE root and a FITC
+ * mean are ignored, nothing of the GPs changes.
+ * Asynchronous on `stream`, no host synchronisation: one launch for the start state and one per pick.  The handle's
+ * scratch (the c columns [n_gp][m][capacity], p and the per-block bests) is allocated by the first call and again
+ * when a capacity or m has grown, a synchronous setup step like gpmpc_gp_reserve; if that fails the call returns
+ * GPMPC_ERR_NOMEM and the handle is unchanged.
+ * Refused: m < 1, m >= n, m > 256, pick_dev NULL (GPMPC_ERR_ARG); a GP not set, set without Linv or a FITC upload,
+ * GPs that differ in their row count (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_gp_redundant(gpmpc_handle* h, int32_t m, int32_t* pick_dev, double* score_dev, int32_t* ok_dev,
+                                void* stream);
 
 /* gpmpc_preprocess followed by an append of the m rows to every GP of the handle, in one stream-ordered call:
  * the rows are staged per GP (X_g [m][d_g], y_g [m]) in scratch of the handle, which holds max_batch rows and is

@@ -28,6 +28,15 @@ ratio of the medians, and the solve's ms per step for scale.
 alternates the sides named, in the order given, and prints the same figures per side, the ratio of the last side's
 median to the first's and the launches one selection queues (the gather, a variance launch per GP, and for greedy
 the V launch, the start state and one launch per row).
+
+`--evict` changes the axis again: every side is the device path with one selection (the first `--select` value,
+greedy by default), and the sides differ in what leaves the full window.
+
+    oldest     GPMPC.observe(evict_oldest=True): gpmpc_gp_drop_oldest inside gpmpc_gp_observe
+    redundant  GPMPC.observe(evict="redundant"): gpmpc_gp_redundant (the start state and one launch per row), then
+               gpmpc_gp_drop_rows on every GP (one launch that sorts, three per block of 16 rows)
+
+    python tools/observe_ab.py --evict oldest redundant
 """
 
 from __future__ import annotations
@@ -47,7 +56,7 @@ for p in (ROOT / "gp-mpc_amd", ROOT):
         sys.path.insert(0, str(p))
 
 
-def run(args, torch, device_data: bool, select: str = "random") -> dict:
+def run(args, torch, device_data: bool, select: str = "random", evict: str = "oldest") -> dict:
     from gpmpc.gp import GaussianProcess
     from gpmpc.gpmpc import GPMPC
     from gpmpc.synthetic import DEFAULT_HYPERS, initial_states, make_training_data
@@ -74,6 +83,7 @@ def run(args, torch, device_data: bool, select: str = "random") -> dict:
     ts = torch.tensor(phase, dtype=torch.int32, device=dev)
     host_obs = [obs[0].cpu().numpy()]
     learn_ms, solve_ms, bad = [], [], 0
+    room_for = dict(evict="redundant") if evict == "redundant" else dict(evict_oldest=True)
     for step in range(steps):
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
@@ -87,12 +97,12 @@ def run(args, torch, device_data: bool, select: str = "random") -> dict:
         # ---- the learning part
         if device_data and select != "random":
             action[step].copy_(u)
-            ctrl.observe(obs[step], action[step], obs[step + 1], m=min(args.rows, B), select=select, evict_oldest=True)
+            ctrl.observe(obs[step], action[step], obs[step + 1], m=min(args.rows, B), select=select, **room_for)
         elif device_data:
             action[step].copy_(u)
             pick = rng.choice(B, min(args.rows, B), replace=False)
             ctrl.observe(obs[step], action[step], obs[step + 1], pick=torch.as_tensor(pick.astype(np.int32)).to(dev),
-                         evict_oldest=True)
+                         **room_for)
         else:
             act = u.cpu().numpy()
             host_obs.append(obs[step + 1].cpu().numpy())
@@ -122,12 +132,17 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=11)
     ap.add_argument("--select", nargs="+", choices=("random", "variance", "greedy"), default=None,
                     help="compare these selections on the device path instead of host against device")
+    ap.add_argument("--evict", nargs="+", choices=("oldest", "redundant"), default=None,
+                    help="compare these eviction rules on the device path (selection: the first --select value, greedy "
+                         "by default)")
     args = ap.parse_args(argv)
 
     import torch
 
     if not torch.cuda.is_available():
         raise SystemExit("observe_ab.py measures on the GPU: no HIP device available")
+    if args.evict:
+        return main_evict(args, torch)
     if args.select:
         return main_select(args, torch)
     runs = {False: [], True: []}
@@ -163,6 +178,31 @@ def main_select(args, torch):
         med["selection_launches"] = launches[name]
         out[name] = med
     first, last = args.select[0], args.select[-1]
+    out[f"{last}_over_{first}"] = out[last]["learn_ms_per_step"] / out[first]["learn_ms_per_step"]
+    print(json.dumps(out))
+
+
+def main_evict(args, torch):
+    from gpmpc.models import get_spec
+
+    select = args.select[0] if args.select else "greedy"
+    runs = {name: [] for name in args.evict}
+    for _ in range(args.repeats):
+        for name in args.evict:
+            runs[name].append(run(args, torch, True, select, name))
+    out = {"config": {k: getattr(args, k) for k in ("model", "horizon", "batch", "capacity", "rows", "steps", "warmup",
+                                                     "repeats", "seed", "evict")}}
+    out["config"]["select"] = select
+    n_gp, m = get_spec(args.model).n_gp, min(args.rows, args.batch)
+    blocks = (m + 15) // 16
+    launches = {"oldest": 3 * blocks * n_gp, "redundant": 1 + m + (1 + 3 * blocks) * n_gp}
+    for name in args.evict:
+        rs = sorted(runs[name], key=lambda r: r["learn_ms_per_step"])
+        med = dict(rs[len(rs) // 2])
+        med["learn_ms_per_step_runs"] = [round(r["learn_ms_per_step"], 4) for r in runs[name]]
+        med["eviction_launches"] = launches[name]
+        out[name] = med
+    first, last = args.evict[0], args.evict[-1]
     out[f"{last}_over_{first}"] = out[last]["learn_ms_per_step"] / out[first]["learn_ms_per_step"]
     print(json.dumps(out))
 
