@@ -199,10 +199,7 @@ struct gpmpc_handle {
     int32_t* order = nullptr;       // cost-ordered dispatch (StateDev::order / cost)
     uint32_t* cost = nullptr;
     double* traj = nullptr;
-    double* plant_params = nullptr;
     double* tgain = nullptr;        // [H][nb][n_unc] tightening gain table (ProblemDev::tgain)
-    double plant_params_host[kMaxParams] = {0};
-    bool plant_params_valid = false;
     GPSlot gp[kMaxGP];
     // optional per-kernel HIP-event timing (bench.py's roofline leg)
     bool profiling = false;
@@ -234,6 +231,7 @@ struct gpmpc_handle {
     hipStream_t last_stream = nullptr;
     hipEvent_t ev_last = nullptr;
     bool ev_last_valid = false;
+    bool tail_unmarked = false;     // last_stream holds work queued after ev_last was recorded (DeferredMark)
     // overlapped steps (gpmpc_solve): the second half's variance and SQP launches run on `side`,
     // forked from and joined back into the caller's stream by two events
     bool overlap = true;            // GPMPC_TUNE_OVERLAP
@@ -262,7 +260,21 @@ static hipError_t order_after_last(gpmpc_handle* h, hipStream_t s) {
             return e;
         }
     }
-    if (h->ev_last_valid && h->last_stream != s) return hipStreamWaitEvent(s, h->ev_last, 0);
+    if (h->last_stream == s) return hipSuccess;
+    if (h->tail_unmarked) {
+        // gpmpc_plant_step's deferred record (DeferredMark), made up for now that a call on another stream needs
+        // it.  If the stream has been destroyed meanwhile the older record stands: it still orders every call that
+        // touched the handle's device state.
+        if (hipEventRecord(h->ev_last, h->last_stream) == hipSuccess) {
+            h->ev_last_valid = true;
+        } else {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(h->last_stream);
+            (void)hipGetLastError();
+        }
+        h->tail_unmarked = false;
+    }
+    if (h->ev_last_valid) return hipStreamWaitEvent(s, h->ev_last, 0);
     return hipSuccess;
 }
 // Records the handle's event on the call's stream when the call returns, whatever it queued.  If
@@ -278,6 +290,19 @@ struct StreamMark {
             h->ev_last_valid = false;
         }
         h->last_stream = s;
+        h->tail_unmarked = false;
+    }
+};
+// gpmpc_plant_step's mark.  The call touches nothing of the handle on the device and closes every step of a control
+// loop, where a second event record per step is a dispatch gap of several microseconds for nothing (the next call comes
+// on the same stream).  So it only notes that its stream holds work behind the last record; order_after_last records
+// the event when a call arrives on another stream.  The stream must still exist then for the launch to be waited for.
+struct DeferredMark {
+    gpmpc_handle* h;
+    hipStream_t s;
+    ~DeferredMark() {
+        h->last_stream = s;
+        h->tail_unmarked = true;
     }
 };
 
@@ -346,7 +371,7 @@ static void free_handle(gpmpc_handle* h) {
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->ev_last) (void)hipEventDestroy(h->ev_last);
     if (h->side) (void)hipStreamDestroy(h->side);
-    for (double* p : {h->x, h->u, h->pi, h->lam, h->var, h->tight, h->traj, h->plant_params, h->tgain, h->lin})
+    for (double* p : {h->x, h->u, h->pi, h->lam, h->var, h->tight, h->traj, h->tgain, h->lin})
         if (p) (void)hipFree(p);
     if (h->has_prev) (void)hipFree(h->has_prev);
     if (h->lin_tag) (void)hipFree(h->lin_tag);
@@ -402,7 +427,6 @@ gpmpc_status gpmpc_create(int32_t model_id, int32_t horizon, int32_t max_batch, 
         {(void**)&h->lin_tag, B * sizeof(int32_t)},
         {(void**)&h->order, B * sizeof(int32_t)},
         {(void**)&h->cost, B * sizeof(uint32_t)},
-        {(void**)&h->plant_params, kMaxParams * sizeof(double)},
         {(void**)&h->scratch_i, 2 * B * sizeof(int32_t)},
         {(void**)&h->scratch_d, 4 * B * sizeof(double)},
     };
@@ -1842,6 +1866,11 @@ gpmpc_status gpmpc_gp_predict(gpmpc_handle* h, int32_t gp_id, const double* Z, i
     if (var && !h->gp[gp_id].linvT) return fail(GPMPC_ERR_STATE, "variance needs Linv");
     if (P == 0) return GPMPC_OK;
     (void)hipSetDevice(h->device);
+    // a reader of the rows, weights, factor and tile pack: it waits for an update queued on another stream, and an
+    // update queued later on another stream waits for it (they rewrite all of these in place)
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
     const GPDev& g = h->P.gp[gp_id];
     PostArgs a{};
     a.Z = Z;
@@ -1858,12 +1887,12 @@ gpmpc_status gpmpc_gp_predict(gpmpc_handle* h, int32_t gp_id, const double* Z, i
         gm.linvT = nullptr;
         a.mean = mean;
         a.var = nullptr;
-        HIPCHK(launch_gp_post(gm, (g.n + 15) / 16 * 16, a, false, (hipStream_t)stream));
+        HIPCHK(launch_gp_post(gm, (g.n + 15) / 16 * 16, a, false, s));
     }
     if (var) {
         a.mean = nullptr;
         a.var = var;
-        HIPCHK(launch_gp_post(g, h->gp[gp_id].npad, a, false, (hipStream_t)stream, h->var_trim ? 0 : 1));
+        HIPCHK(launch_gp_post(g, h->gp[gp_id].npad, a, false, s, h->var_trim ? 0 : 1));
     }
     return GPMPC_OK;
 }
@@ -1875,7 +1904,10 @@ gpmpc_status gpmpc_gp_mean_grad(gpmpc_handle* h, int32_t gp_id, const double* Z,
     if (P < 0 || (P > 0 && !Z)) return fail(GPMPC_ERR_ARG, "bad points");
     if (P == 0) return GPMPC_OK;
     (void)hipSetDevice(h->device);
-    HIPCHK(launch_gp_mean_grad(h->P.gp[gp_id], Z, P, mean, grad, (hipStream_t)stream));
+    hipStream_t s = (hipStream_t)stream;   // ordered as gpmpc_gp_predict is: it reads the rows and the tile pack
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    HIPCHK(launch_gp_mean_grad(h->P.gp[gp_id], Z, P, mean, grad, s));
     return GPMPC_OK;
 }
 
@@ -1917,15 +1949,12 @@ gpmpc_status gpmpc_plant_step(gpmpc_handle* h, int32_t batch, const double* para
     if (batch < 1) return fail(GPMPC_ERR_ARG, "batch out of range");
     (void)hipSetDevice(h->device);
     hipStream_t s = (hipStream_t)stream;
-    bool same = h->plant_params_valid;
-    for (int i = 0; i < h->md.nparams; ++i) same = same && (h->plant_params_host[i] == params[i]);
-    if (!same) {  // synchronous upload of a 16-double table, only when the parameters change
-        for (int i = 0; i < kMaxParams; ++i) h->plant_params_host[i] = i < h->md.nparams ? params[i] : 0.0;
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipMemcpy(h->plant_params, h->plant_params_host, sizeof(h->plant_params_host), hipMemcpyHostToDevice));
-        h->plant_params_valid = true;
-    }
-    HIPCHK(launch_plant(h->model, h->plant_params, h->P.dt, x, u, x_next, tstep, batch, s));
+    // x and u are as a rule gpmpc_solve's outputs and tstep its next input: the call is ordered like the others
+    HIPCHK(order_after_last(h, s));
+    DeferredMark mark{h, s};
+    PlantParams p{};   // by value: the launch keeps the parameters of its own call (no table of the handle)
+    for (int i = 0; i < h->md.nparams; ++i) p.v[i] = params[i];
+    HIPCHK(launch_plant(h->model, p, h->P.dt, x, u, x_next, tstep, batch, s));
     return GPMPC_OK;
 }
 

@@ -804,8 +804,10 @@ hipError_t launch_gp_post(const GPDev& g, int npad, const PostArgs& a, bool from
 }
 
 // ---------------------------------------------------------------------------- plant
+// The parameters travel by value in the kernel arguments: a queued launch integrates with the ones its call was
+// given, whatever later calls (on any stream) pass, and no table of the handle is read or rewritten.
 template <int ID>
-__global__ void plant_step_kernel(const double* __restrict__ params, double dt, const double* __restrict__ x,
+__global__ void plant_step_kernel(PlantParams params, double dt, const double* __restrict__ x,
                                   const double* __restrict__ u, double* __restrict__ xn, int32_t* tstep, int B) {
     using M = Model<ID>;
     constexpr int NX = M::NX, NU = M::NU;
@@ -813,7 +815,7 @@ __global__ void plant_step_kernel(const double* __restrict__ params, double dt, 
     if (b >= B) return;
     double p[kMaxParams];
 #pragma unroll
-    for (int i = 0; i < kMaxParams; ++i) p[i] = params[i];
+    for (int i = 0; i < kMaxParams; ++i) p[i] = params.v[i];
     double xs[NX], us[NU], k[NX], acc[NX], xi[NX];
     const double gm[kMaxGP] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -834,7 +836,7 @@ __global__ void plant_step_kernel(const double* __restrict__ params, double dt, 
     if (tstep != nullptr) tstep[b] += 1;
 }
 
-hipError_t launch_plant(int model, const double* params, double dt, const double* x, const double* u, double* xn,
+hipError_t launch_plant(int model, const PlantParams& params, double dt, const double* x, const double* u, double* xn,
                         int32_t* tstep, int B, hipStream_t stream) {
     const int blocks = (B + 63) / 64;
     switch (model) {

@@ -600,7 +600,10 @@ hipError_t launch_gp_mean_grad(const GPDev& g, const double* Z, int P, double* m
 hipError_t launch_gp_post(const GPDev& g, int npad, const PostArgs& a, bool from_state, hipStream_t stream,
                           int var_full = 0);   // PostBatch::var_full
 hipError_t launch_gp_post_batch(const PostBatch& pb, bool from_state, hipStream_t stream);
-hipError_t launch_plant(int model, const double* params, double dt, const double* x, const double* u, double* xn,
+struct PlantParams {   // gpmpc_plant_step's parameter vector, a kernel argument (entries past the model's are 0)
+    double v[kMaxParams];
+};
+hipError_t launch_plant(int model, const PlantParams& params, double dt, const double* x, const double* u, double* xn,
                         int32_t* tstep, int B, hipStream_t stream);
 
 }  // namespace gpmpc

@@ -10,9 +10,17 @@
  * Threading: one handle per GPU/process, driven by one host thread at a time
  * (the reference drives one acados solver from one Python thread, gpmpc/gpmpc.py:105-107).
  * Streams: every call queues its work on its stream argument.  The handle's device state is
- * shared by all of them, so each call that touches it ends by recording a handle-owned event on
- * its stream, and a call on a different stream first makes its stream wait for that event
- * (hipStreamWaitEvent: no host synchronisation, and the previous stream may already be gone).
+ * shared by all of them, so each call that takes the handle and a stream ends by recording a
+ * handle-owned event on its stream, and a call on a different stream first makes its stream wait
+ * for that event (hipStreamWaitEvent: no host synchronisation, and the previous stream may already
+ * be gone).  Consecutive calls on one handle therefore run in the order they were made, whatever
+ * their streams: a reader (gpmpc_gp_predict, gpmpc_gp_mean_grad, the gpmpc_get_* copies) sees what
+ * the calls before it wrote, and an update queued after it waits until it has read.  gpmpc_plant_step,
+ * which closes every step of a control loop, defers its record until a call arrives on another stream
+ * (on one stream the record would only cost a dispatch gap): its stream must still exist then.  Two calls stand
+ * outside the rule because they touch nothing of the handle on the device: gpmpc_gp_posterior takes
+ * no handle, and gpmpc_preprocess carries its model parameters by value; their buffers are the
+ * caller's to order.  (tests/stream_order_util.py lists every stream-taking call under one of the two.)
  * The library reads no environment variables: every option is an explicit call.
  */
 #ifndef GPMPC_MI355X_H
@@ -375,7 +383,10 @@ gpmpc_status gpmpc_gp_posterior(int32_t n, int32_t d, int32_t npad, const double
                                 double* mean, double* var, int32_t with_noise, void* stream);
 
 /* Synthetic plant: x_next = RK4(prior-form dynamics with `params`, no GP) for B instances,
- * tstep += 1 if tstep != NULL (crazyflow env.step replacement, scripts/run_gp_mpc.py:59). */
+ * tstep += 1 if tstep != NULL (crazyflow env.step replacement, scripts/run_gp_mpc.py:59).
+ * params (host) is read before the call returns and travels to the kernel by value: a queued launch
+ * integrates with the parameters of its own call, whatever later calls pass on any stream.  No
+ * host synchronisation, whether the parameters change or not. */
 gpmpc_status gpmpc_plant_step(gpmpc_handle* h, int32_t batch, const double* params, const double* x,
                               const double* u, double* x_next, int32_t* tstep, void* stream);
 
