@@ -67,6 +67,7 @@ struct GPSlot {
     double *app = nullptr, *drp = nullptr, *rfc = nullptr;   // scratch of gpmpc_gp_append / _drop_oldest / _refactor
     double* fit = nullptr;         // tile partials and state block of gpmpc_gp_mll / _fit
     double* love = nullptr;        // Lanczos vectors, partial sums and state of gpmpc_gp_love_root
+    double* ind = nullptr;         // d, bests, row state and state words of gpmpc_gp_inducing (InducingLayout)
     double* vroot = nullptr;       // LOVE root (tightening only), its padded columns and its rank
     int vroot_cols = 0, vroot_rank = 0;
     // FITC mean built by gpmpc_gp_fitc, an overlay on the exact mean: its rows, tile pack and indices (FitcOut) and
@@ -74,11 +75,12 @@ struct GPSlot {
     double *fitc = nullptr, *fitc_ws = nullptr;
     int fitc_M = 0, fitc_ws_m = 0, fitc_ws_c = 0;
     // The slot's device buffers: the kReserved ones gpmpc_gp_reserve replaces, then the others
-    static constexpr int kReserved = 9, kBuffers = 13;
+    static constexpr int kReserved = 10, kBuffers = 14;
     static constexpr double* GPSlot::*kBuffer[kBuffers] = {&GPSlot::rows,  &GPSlot::tiles, &GPSlot::linvT,
                                                             &GPSlot::linvT_alt, &GPSlot::app, &GPSlot::drp,
-                                                            &GPSlot::rfc, &GPSlot::fit, &GPSlot::love, &GPSlot::vrows,
-                                                            &GPSlot::vroot, &GPSlot::fitc, &GPSlot::fitc_ws};
+                                                            &GPSlot::rfc, &GPSlot::fit, &GPSlot::love, &GPSlot::ind,
+                                                            &GPSlot::vrows, &GPSlot::vroot, &GPSlot::fitc,
+                                                            &GPSlot::fitc_ws};
     hipError_t release(int count) {   // frees and clears the first `count` of them; returns the first error
         hipError_t first = hipSuccess;
         for (int i = 0; i < count; ++i) {
@@ -131,6 +133,14 @@ struct FitcLayout {
     size_t m, c, A = 0, lt1 = m * m, lt2 = 2 * m * m, dinv = 3 * m * m, ginv = dinv + 16 * m, t = ginv + c, u = t + c,
               p = u + m, q = p + m, lmask = q + m, smask = lmask + c / 2, flag = smask + m / 2, end = flag + 1;
 };
+// Scratch of gpmpc_gp_inducing for a capacity of c (padded) rows, in doubles: d [2][c] | the blocks' best scores
+// [2][c/16] | their indices [2][c/16] int32 | the rows' state [c] int32 | the state words (gpmpc_common.h kInd*).
+// The l columns go into the second factor buffer.
+struct InducingLayout {
+    size_t c, nb = c / kSelectBlock, d = 0, bval = 2 * c, bidx = bval + 2 * nb, state = bidx + nb,
+              flag = state + c / 2, end = flag + kIndInts / 2;
+};
+static_assert(kSelectBlock == 16, "InducingLayout takes its blocks to be the 16 rows a capacity is padded to");
 // what it installs: rows [m][4] | tX, tW [m/16][64] each | the indices [m] int32
 struct FitcOut {
     size_t m, rows = 0, tX = 4 * m, tW = 8 * m, idx = 12 * m, end = idx + m / 2;
@@ -655,6 +665,7 @@ static const GPUpdate kFit{"fit", "is fitted", "the old factor", &GPSlot::fit};
 // (root_of null: an installed root is no obstacle, the call replaces it)
 static const GPUpdate kLove{"the LOVE root", "has its LOVE root built", nullptr, &GPSlot::love, true};
 static const GPUpdate kFitc{"the FITC mean", "has its FITC mean built", nullptr, &GPSlot::rfc, true};
+static const GPUpdate kInducing{"the inducing rows' selection", "has its inducing rows picked", nullptr, &GPSlot::ind, true};
 
 // What the three updates ask first, in this order (bad_args: what is wrong with the call's own arguments, or
 // null).  gpmpc_gp_reserve asks the same up to the exact upload (factor = false).
@@ -703,6 +714,7 @@ gpmpc_status gpmpc_gp_reserve(gpmpc_handle* h, int32_t gp_id, int32_t capacity) 
         {&fresh.rfc, lin ? RefactorLayout{cpad}.end : 0, true},
         {&fresh.fit, lin ? FitLayout{cpad}.end : 0, true},
         {&fresh.love, lin ? LoveLayout{cpad}.end : 0, true},
+        {&fresh.ind, lin ? InducingLayout{cpad}.end : 0, true},
     };
     hipError_t e = hipSuccess;
     auto undo = [&](gpmpc_status st, const char* what) {
@@ -1299,6 +1311,66 @@ gpmpc_status gpmpc_gp_fitc(gpmpc_handle* h, int32_t gp_id, int32_t M, const int3
     g.ntile = mpad / 16;
     bump_lin(h);
     if (ok_out) *ok_out = 1;
+    return GPMPC_OK;
+}
+
+gpmpc_status gpmpc_gp_inducing(gpmpc_handle* h, int32_t gp_id, int32_t M, double tol, int32_t* idx_dev,
+                               double* gain_dev, double* resid_dev, int32_t* count_out) {
+    const char* bad = nullptr;
+    if (M < 1) bad = "M must be 1 .. n";
+    else if (!(std::isfinite(tol) && tol >= 0.0)) bad = "tol must be finite and not negative";
+    else if (!idx_dev) bad = "no room for the picks (idx_dev is NULL)";
+    // (a LOVE root and a FITC mean are no obstacle: both were built in the second factor buffer by calls that had
+    // finished with it when they returned, and neither keeps anything there)
+    const gpmpc_status ready = gp_update_ready(h, gp_id, kInducing, bad);
+    if (ready != GPMPC_OK) return ready;
+    GPSlot& gs = h->gp[gp_id];
+    const GPDev& g = h->P.gp[gp_id];
+    const int n = g.nv;   // (the training rows: g.n counts the inducing rows under a FITC mean)
+    if (M > n) return fail(GPMPC_ERR_ARG, "M must be 1 .. n: " + std::to_string(M) + " inducing rows of " +
+                                              std::to_string(n) + " training rows asked for");
+    (void)hipSetDevice(h->device);
+    // on a stream of the handle's own, behind the handle's last call, and drained before the call returns
+    HIPCHK(ensure_side(h));
+    hipStream_t s = h->side;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    const int cpad = (gs.cap + 15) / 16 * 16;
+    const InducingLayout lay{(size_t)cpad};
+    GPInducing a{};
+    a.rows = gs.rows;
+    a.linvT = gs.linvT;
+    a.lcol = gs.linvT_alt;
+    a.npad = gs.npad;
+    a.n = n;
+    a.M = M;
+    a.d = h->md.gp_dim[gp_id];
+    a.ld = cpad;
+    a.nblk = (n + kSelectBlock - 1) / kSelectBlock;
+    a.c = -0.5 * g.inv_ell2;
+    a.sf2 = g.sf2;
+    a.tol = tol;
+    a.dd = gs.ind + lay.d;
+    a.bval = gs.ind + lay.bval;
+    a.bidx = reinterpret_cast<int32_t*>(gs.ind + lay.bidx);
+    a.state = reinterpret_cast<int32_t*>(gs.ind + lay.state);
+    a.flag = reinterpret_cast<int32_t*>(gs.ind + lay.flag);
+    a.idx = idx_dev;
+    a.gain = gain_dev;
+    a.resid = resid_dev;
+    HIPCHK(launch_gp_inducing_begin(a, s));
+    // the count is read back once per kInducingQueue picks; what is queued past the stop changes nothing
+    constexpr int kInducingQueue = 64;
+    int32_t count = -1;
+    for (int done = 0; done < M && count < 0;) {
+        const int q = std::min(kInducingQueue, M - done);
+        for (int i = 0; i < q; ++i) HIPCHK(launch_gp_inducing_step(a, done + i, s));
+        done += q;
+        HIPCHK(hipMemcpyAsync(&count, a.flag + kIndCount, sizeof(count), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    if (count < 0 || count > M) return fail(GPMPC_ERR_HIP, "gpmpc_gp_inducing: the selection left no count");
+    if (count_out) *count_out = count;
     return GPMPC_OK;
 }
 

@@ -1,7 +1,9 @@
 // GP training rows from transitions on the device (gpmpc_preprocess, gpmpc_gp_informative, gpmpc_gp_observe): the
 // device restatement of GPMPC.preprocess_data (gpmpc/gpmpc.py, the reference's gpmpc/gpmpc.py:113-151) and the
 // counting rank of the points' variance scores.  One thread per output row; nothing here synchronises the host.
-// Below them the greedy conditional-variance selection (gpmpc_gp_select): the V kernel and the pick loop.
+// Below them the greedy conditional-variance selection (gpmpc_gp_select): the V kernel and the pick loop; and the
+// greedy choice of a GP's FITC inducing rows among its own training rows (gpmpc_gp_inducing): the same pick loop
+// over a grid of the rows, with an end by tolerance.
 #include "gp_tile.h"
 #include "gpmpc_common.h"
 #include "models.h"
@@ -124,16 +126,20 @@ constexpr int kSelWaves = 4;
 constexpr int kSelCT = 16;
 constexpr int kSelStride = 16 * (kSelCT | 1);   // odd number of tiles per LDS row, as gp_post_kernel's
 
-// k_g(z, z') of two gathered candidates, the operations of the variance kernels' kernel value
-__device__ __forceinline__ double select_kernel_value(const GPSelectGP& g, const double* zi, const double* zj) {
+// k(z, z') of two inputs of d columns, the operations of the variance kernels' kernel value
+__device__ __forceinline__ double select_rbf(int d, double c, double sf2, const double* zi, const double* zj) {
     double q = 0.0;
 #pragma unroll
     for (int dd = 0; dd < 3; ++dd) {
-        const int k = dd < g.d ? dd : 0;   // (nothing is read past the GP's own columns)
-        const double df = (dd < g.d) ? zj[k] - zi[k] : 0.0;
+        const int k = dd < d ? dd : 0;   // (nothing is read past the GP's own columns)
+        const double df = (dd < d) ? zj[k] - zi[k] : 0.0;
         q = fma(df, df, q);
     }
-    return g.sf2 * exp_rbf(g.c * q);
+    return sf2 * exp_rbf(c * q);
+}
+// k_g(z, z') of two gathered candidates
+__device__ __forceinline__ double select_kernel_value(const GPSelectGP& g, const double* zi, const double* zj) {
+    return select_rbf(g.d, g.c, g.sf2, zi, zj);
 }
 
 __global__ __launch_bounds__(64 * kSelWaves) void gp_select_v_kernel(const GPSelect a) {
@@ -386,7 +392,171 @@ __global__ __launch_bounds__(kSelThreads) void gp_select_step_kernel(const GPSel
     }
 }
 
+// ------------------------------------------------------------------ greedy inducing rows (gpmpc_gp_inducing)
+// The same pivoted Cholesky over a GP's own training rows with the prior covariance: d_i = sf2 at the start, no V, no
+// noise, and an end as soon as no open row's score d_i / sf2 exceeds tol.  The grid runs over the n rows and the
+// history grows to M columns (2000 at the large quad3d size, against gp_select's 256), so what gp_select_step_kernel
+// reads straight from memory inside its sum, the pivot row l_s[j], is staged here: it is a gather over the columns
+// (stride ld), the same for every row of the workgroup, and read from memory inside the sum it doubles the loads of
+// the dependent loop with lines of which 8 bytes are used.  Each chunk of kSelThreads columns is gathered once, one
+// column per thread and all in flight together, into LDS, where the kSelectBlock rows of a part read one address
+// (a broadcast) and a wave's four parts four consecutive ones; the rows' own entries are loaded kSelectParts at a
+// time ahead of their sums.
+
+// The start state: d = sf2 and open for a live row, 0 and closed for an inert one (a zero on the factor's diagonal),
+// each block's best (every live score is exactly 1: the lowest live index wins), the outputs' tails (-1, NaN) in
+// full, the state words.  One wave = 64 / kSelectBlock row blocks.
+__global__ __launch_bounds__(64) void gp_inducing_init_kernel(const GPInducing a) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const bool valid = i < a.n;
+    SelectBest b{0.0, kSelNone, kSelNone};
+    if (valid) {
+        const bool live = a.linvT[(size_t)i * a.npad + i] != 0.0;
+        a.dd[i] = live ? a.sf2 : 0.0;
+        a.state[i] = live ? 0 : 3;
+        b = select_candidate(a.sf2 / a.sf2, i, live);
+        if (i < a.M) {
+            a.idx[i] = -1;
+            if (a.gain != nullptr) a.gain[i] = __longlong_as_double(0x7ff8000000000000ll);
+        }
+    }
+    b = select_group_best(b);
+    const int blk = i / kSelectBlock;
+    if (threadIdx.x % kSelectBlock == 0 && blk < a.nblk) {
+        a.bval[blk] = b.val;
+        a.bidx[blk] = b.idx;
+    }
+    if (i == 0) {
+        a.flag[kIndStop] = 0;
+        a.flag[kIndCount] = -1;
+    }
+}
+
+// Pick t.  Every workgroup reduces the blocks' bests of the previous launch to j_t, as gp_select_step_kernel does;
+// when the selection has stopped, or stops here (no open row with a finite score above tol), it leaves the stop for
+// the next launch, the count and the residuals, and returns, uniformly.  Otherwise its kSelectBlock rows times
+// kSelectParts parts form l_t: part q sums the columns s = q, q + 16, .. in order, the parts are added as a balanced
+// tree, ((0 + 1) + (2 + 3)) + .., so a row's values do not depend on where it sits.
+__global__ __launch_bounds__(kSelThreads) void gp_inducing_step_kernel(const GPInducing a, const int t) {
+    __shared__ double sval[kSelThreads];
+    __shared__ int sidx[kSelThreads];
+    __shared__ double lj[kSelThreads];
+    __shared__ double part[kSelectParts][kSelectBlock];
+    const int tid = threadIdx.x;
+    const int cur = t & 1, nxt = cur ^ 1;
+    const bool first = blockIdx.x == 0 && tid == 0;
+    if (a.flag[kIndStop + cur] != 0) {   // (written by the launch before this one; uniform)
+        if (first) a.flag[kIndStop + nxt] = 1;
+        return;
+    }
+    SelectBest b{0.0, kSelNone, kSelNone};
+    for (int k = tid; k < a.nblk; k += kSelThreads) {
+        const size_t at = (size_t)cur * a.nblk + k;
+        b = select_merge(b, SelectBest{a.bval[at], a.bidx[at], kSelNone});
+    }
+    sval[tid] = b.val;
+    sidx[tid] = b.idx;
+    __syncthreads();
+    for (int s = kSelThreads / 2; s >= 1; s >>= 1) {
+        if (tid < s) {
+            const SelectBest r = select_merge(SelectBest{sval[tid], sidx[tid], kSelNone},
+                                              SelectBest{sval[tid + s], sidx[tid + s], kSelNone});
+            sval[tid] = r.val;
+            sidx[tid] = r.idx;
+        }
+        __syncthreads();
+    }
+    const int j = sidx[0];
+    const double gain = sval[0];
+    const int ci = tid % kSelectBlock, kp = tid / kSelectBlock;
+    const int i = blockIdx.x * kSelectBlock + ci;
+    const bool valid = i < a.n;
+    const int ii = valid ? i : a.n - 1;
+    const size_t ld = a.ld;
+    const double* din = a.dd + (size_t)cur * ld;
+    double* dout = a.dd + (size_t)nxt * ld;
+    if (j < 0 || j >= a.n || !(gain > a.tol)) {   // the end: count = t (uniform; a score kept as a best is finite)
+        if (first) {
+            a.flag[kIndStop + nxt] = 1;
+            a.flag[kIndCount] = t;
+        }
+        if (kp == 0 && valid && a.resid != nullptr) a.resid[i] = din[i];
+        return;
+    }
+    if (first) {
+        a.idx[t] = j;
+        if (a.gain != nullptr) a.gain[t] = gain;
+        a.flag[kIndStop + nxt] = 0;
+        if (t == a.M - 1) a.flag[kIndCount] = a.M;
+    }
+    const double pv = din[j];   // (= gain sf2 > 0)
+    double acc = 0.0;
+    for (int s0 = 0; s0 < t; s0 += kSelThreads) {
+        const int cnt = min(kSelThreads, t - s0);
+        __syncthreads();   // the previous chunk has been read
+        lj[tid] = tid < cnt ? a.lcol[(size_t)(s0 + tid) * ld + j] : 0.0;
+        double x[kSelectParts];
+#pragma unroll
+        for (int k = 0; k < kSelectParts; ++k) {
+            const int q = kp + kSelectParts * k;
+            x[k] = q < cnt ? a.lcol[(size_t)(s0 + q) * ld + ii] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kSelectParts; ++k) {
+            const int q = kp + kSelectParts * k;
+            if (q < cnt) acc = fma(x[k], lj[q], acc);
+        }
+    }
+    part[kp][ci] = acc;
+    __syncthreads();
+    if (kp == 0) {   // (the first kSelectBlock lanes of wave 0)
+        SelectBest nb{0.0, kSelNone, kSelNone};
+        if (valid) {
+            double r[kSelectParts];
+#pragma unroll
+            for (int q = 0; q < kSelectParts; ++q) r[q] = part[q][ci];
+#pragma unroll
+            for (int w = kSelectParts / 2; w >= 1; w >>= 1)
+#pragma unroll
+                for (int q = 0; q < w; ++q) r[q] = r[2 * q] + r[2 * q + 1];
+            int st = a.state[i];
+            const double k = select_rbf(a.d, a.c, a.sf2, a.rows + (size_t)i * 4, a.rows + (size_t)j * 4);
+            const double l = (st & 2) ? 0.0 : (k - r[0]) / sqrt(pv);
+            a.lcol[(size_t)t * ld + i] = l;
+            const double dn = din[i] - l * l;
+            dout[i] = dn;
+            if (a.resid != nullptr && t == a.M - 1) a.resid[i] = dn;
+            if (i == j) a.state[i] = st = st | 1;
+            nb = select_candidate(dn / a.sf2, i, !(st & 1));
+        }
+        nb = select_group_best(nb);
+        if (tid == 0) {
+            const size_t at = (size_t)nxt * a.nblk + blockIdx.x;
+            a.bval[at] = nb.val;
+            a.bidx[at] = nb.idx;
+        }
+    }
+}
+
 }  // namespace
+
+static bool inducing_args_ok(const GPInducing& a) {
+    return a.n >= 1 && a.M >= 1 && a.M <= a.n && a.n <= a.ld && a.n <= a.npad && a.npad >= 16 && a.npad % 16 == 0 &&
+           a.nblk == (a.n + kSelectBlock - 1) / kSelectBlock && a.d >= 1 && a.d <= 3 && a.idx != nullptr;
+}
+
+hipError_t launch_gp_inducing_begin(const GPInducing& a, hipStream_t stream) {
+    if (!inducing_args_ok(a)) return hipErrorInvalidValue;
+    GP_LAUNCH(gp_inducing_init_kernel, dim3((a.n + 63) / 64), dim3(64), stream, a);
+    return hipSuccess;
+}
+
+hipError_t launch_gp_inducing_step(const GPInducing& a, int t, hipStream_t stream) {
+    if (!inducing_args_ok(a) || t < 0 || t >= a.M) return hipErrorInvalidValue;
+    GP_LAUNCH(gp_inducing_step_kernel, dim3(a.nblk), dim3(kSelThreads), stream, a, t);
+    return hipSuccess;
+}
 
 hipError_t launch_gp_select(const GPSelect& a, hipStream_t stream) {
     if (a.P < 1 || a.m < 1 || a.m > a.P || a.m > kSelectMaxPicks || a.P > a.ldp || a.n_gp < 1 || a.n_gp > kMaxGP ||

@@ -557,6 +557,33 @@ struct GPSelect {
 };
 // V for every GP (one launch), the start state, then one launch per pick
 hipError_t launch_gp_select(const GPSelect& a, hipStream_t stream);
+// Greedy choice of up to M of a GP's n training rows as FITC inducing rows (gp_observe.hip; gpmpc_gp_inducing fills
+// it): a pivoted partial Cholesky of the prior covariance k(X, X), no likelihood noise, that ends when no open row's
+// residual prior variance exceeds tol sf2.  The grid runs over the training rows; everything but the outputs is
+// scratch of the GP.
+struct GPInducing {
+    const double* rows;   // [>= npad][4], the training rows (the slot's exact rows): the inputs
+    const double* linvT;  // [npad][npad], the live factor: only its diagonal is read (zero: an inert row)
+    double* lcol;         // [M][ld]: l_t[i] (the second factor buffer)
+    int32_t npad, n, M, d;
+    int32_t ld;           // the padded capacity: stride of the l columns and of d
+    int32_t nblk;         // ceil(n / kSelectBlock)
+    double c, sf2, tol;   // c = -1 / (2 ell^2)
+    double* dd;           // [2][ld]: step t reads half t & 1 and writes the other
+    int32_t* state;       // [ld]: bit 0 closed (picked or inert), bit 1 inert
+    double* bval;         // [2][nblk]: each block's best score among its open rows
+    int32_t* bidx;        // [2][nblk]: its index (INT_MAX: none)
+    int32_t* flag;        // the state words (kInd* below)
+    int32_t* idx;         // [M]: the picks, then -1
+    double* gain;         // [M] or null: the scores at which they were picked, then NaN
+    double* resid;        // [n] or null: the final d
+};
+// The state words: stopped, as step t reads it at [t & 1] and leaves it at [(t + 1) & 1]; the picks made (-1 while
+// the selection runs: the stopping step or step M - 1 writes it)
+enum : int { kIndStop = 0, kIndCount = 2, kIndInts = 4 };
+// the start state and the outputs' tails; pick t (nothing once the state says stopped)
+hipError_t launch_gp_inducing_begin(const GPInducing& a, hipStream_t stream);
+hipError_t launch_gp_inducing_step(const GPInducing& a, int t, hipStream_t stream);
 hipError_t launch_gp_append(const GPAppend& a, hipStream_t stream);
 hipError_t launch_gp_drop(const GPDrop& a, hipStream_t stream);
 hipError_t launch_gp_drop_prep(const GPDropPrep& a, hipStream_t stream);

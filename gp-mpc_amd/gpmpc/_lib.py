@@ -48,6 +48,7 @@ SIGNATURES = {
     "gpmpc_get_gp_variance_root": (_I, [_P, _I, POINTER(_I), POINTER(_I), _P, _P]),
     "gpmpc_gp_fitc": (_I, [_P, _I, _I, _P, _P, _D, POINTER(_I), _P]),
     "gpmpc_get_gp_fitc": (_I, [_P, _I, POINTER(_I), _P, _P, _P]),
+    "gpmpc_gp_inducing": (_I, [_P, _I, _I, _D, _P, _P, _P, POINTER(_I)]),
     "gpmpc_gp_size": (_I, [_P, _I, POINTER(_I), POINTER(_I)]),
     "gpmpc_use_gp": (_I, [_P, _I]),
     "gpmpc_set_gp_variance_root": (_I, [_P, _I, _I, _I, _P]),

@@ -36,17 +36,22 @@ class GPMPC:
     variance: str = "exact"
     # where the sparse (FITC) mean is built: "host" (precompute_sparse_posterior_mean, uploaded once; no
     # device-side update of the GPs) or "device" (BatchSolver.fitc_gp on the uploaded exact GPs, rebuilt after
-    # every update); the jitter the device build adds to the diagonal of K_ss; its last draw of inducing rows
+    # every update); the jitter the device build adds to the diagonal of K_ss; its last draw of inducing rows.
+    # fitc_select: how the device build chooses them, "random" (the reference's np_random.choice, one draw for all
+    # GPs) or "greedy" (BatchSolver.inducing_gp per GP, down to a residual prior variance of fitc_tol outputscales;
+    # fitc_idx is then a list of per-GP arrays)
     fitc: str = "host"
     fitc_jitter: float = 0.0
-    fitc_idx: np.ndarray | None = None
+    fitc_idx: np.ndarray | list | None = None
+    fitc_select: str = "random"
+    fitc_tol: float = 1e-4
 
     def __init__(self, symbolic_model, traj: np.ndarray | None = None, prior_params: dict | None = None,
                  horizon: int = 25, q_mpc: list | None = None, r_mpc: list | None = None, sparse_gp: bool = False,
                  prob: float = 0.955, max_gp_samples: int = 30, seed: int = 1337, device: str = "cuda",
                  output_dir: Path | None = None, batch: int = 1, variance_inputs: str = "reference",
                  variance: str = "love", gp_capacity: int | None = None, fitc: str = "host",
-                 fitc_jitter: float = 0.0, **solver_kw):
+                 fitc_jitter: float = 0.0, fitc_select: str = "random", fitc_tol: float = 1e-4, **solver_kw):
         spec = (symbolic_model if isinstance(symbolic_model, ModelSpec) else get_spec(symbolic_model)).copy()
         # "reference": the variance input map of `gpmpc/gpmpc.py:437-444` (for quad3d it indexes the
         # full state-input vector with the GP-input-space indices); "dynamics": each GP's own inputs
@@ -75,7 +80,14 @@ class GPMPC:
             raise ValueError("fitc must be 'host' or 'device'")
         if fitc == "device" and not sparse_gp:
             raise ValueError("fitc='device' builds the sparse (FITC) mean: it needs sparse_gp=True")
+        if fitc_select not in ("random", "greedy"):
+            raise ValueError("fitc_select must be 'random' or 'greedy'")
+        if fitc_select == "greedy" and not (sparse_gp and fitc == "device"):
+            raise ValueError("fitc_select='greedy' picks the inducing rows on the device: it needs sparse_gp=True, "
+                             "fitc='device'")
         self.fitc = fitc
+        self.fitc_select = fitc_select
+        self.fitc_tol = float(fitc_tol)
         self.fitc_jitter = float(fitc_jitter)
         self.fitc_idx = None
         self.output_dir = output_dir
@@ -243,12 +255,22 @@ class GPMPC:
         """The FITC mean of every GP on the solver handle, built on the device (``BatchSolver.fitc_gp``) on one
         draw of ``min(n, max_gp_samples)`` inducing rows over the handle's n current training rows: the
         ``np_random.choice`` call of ``precompute_sparse_posterior_mean``, so the same seed gives the same
-        rows.  The draw is kept as ``fitc_idx``."""
+        rows.  The draw is kept as ``fitc_idx``.
+
+        With ``fitc_select="greedy"`` the rows are chosen on the device instead, per GP
+        (``BatchSolver.inducing_gp`` with at most ``min(n, max_gp_samples)`` rows and ``fitc_tol``): ``fitc_idx``
+        is then a list of per-GP int32 arrays, the GPs may end with different numbers of inducing rows
+        (``solver.fitc_sizes``), and ``np_random`` is not consumed."""
         s = self.solver
         n = s.gp_size(0)[0]
-        self.fitc_idx = np.asarray(self.np_random.choice(range(n), size=min(n, self.max_gp_samples), replace=False))
+        greedy = self.fitc_select == "greedy"
+        if greedy:
+            self.fitc_idx = [s.inducing_gp(g, min(s.gp_size(g)[0], self.max_gp_samples), self.fitc_tol).cpu().numpy()
+                             for g in range(self.model.n_gp)]
+        else:
+            self.fitc_idx = np.asarray(self.np_random.choice(range(n), size=min(n, self.max_gp_samples), replace=False))
         for g, gp in enumerate(self.gaussian_process):
-            if not s.fitc_gp(g, self.fitc_idx, gp.train_targets, self.fitc_jitter):
+            if not s.fitc_gp(g, self.fitc_idx[g] if greedy else self.fitc_idx, gp.train_targets, self.fitc_jitter):
                 hint = "; try fitc_jitter > 0" if self.fitc_jitter == 0.0 else ""
                 raise _lib.GPMPCError(f"GP {g}: the FITC mean could not be built (a pivot or a Gamma was not positive, "
                                       f"or an inducing row is inert); the GP is on the exact mean{hint}")

@@ -478,6 +478,28 @@ class BatchSolver:
             self.fitc_sizes[int(gp_id)] = int(idx.shape[0])
         return ok.value
 
+    def inducing_gp(self, gp_id: int, M: int, tol: float = 0.0, gains: bool = False, resid: bool = False):
+        """Choose up to ``M`` of the n training rows of the handle's GP ``gp_id`` as FITC inducing rows, on the
+        device (gpmpc_gp_inducing): greedily by residual prior variance, a pivoted partial Cholesky of k(X, X) at
+        the GP's current hyperparameters, which ends when no row's residual variance exceeds ``tol`` times the
+        outputscale.  Near-copies of a picked row are never picked, and with ``tol > 0`` the picks give
+        ``fitc_gp(..., jitter=0)`` pivots bounded below.  Inert rows are never picked.  Returns ``idx``, the device
+        int32 picks in pick order (their count is its length, at most M), then with ``gains=True`` the scores at
+        which they were picked (non-increasing up to rounding, 1.0 first) and with ``resid=True`` the (n,) residual
+        variances (0 for an inert row).  The call synchronises the current stream first and returns with its work
+        completed (it runs on a stream of the handle's own).  Needs ``reserve_gp``; nothing of the GP changes."""
+        M = int(M)
+        n = self.gp_size(gp_id)[0]
+        idx = torch.empty(max(M, 1), dtype=torch.int32, device=self.device)   # (never empty: the refusal is the library's)
+        gain = torch.empty(max(M, 1), dtype=torch.float64, device=self.device) if gains else None
+        res = torch.empty(n, dtype=torch.float64, device=self.device) if resid else None
+        torch.cuda.current_stream(self.device).synchronize()   # (nothing still queued on memory the outputs reuse)
+        count = ctypes.c_int32()
+        _lib.check(self.lib.gpmpc_gp_inducing(self._h, int(gp_id), M, float(tol), idx.data_ptr(), _lib.ptr(gain),
+                                              _lib.ptr(res), ctypes.byref(count)))
+        out = (idx[:count.value], None if gain is None else gain[:count.value], res)
+        return out[0] if not (gains or resid) else tuple(t for t in out if t is not None)
+
     def drop_fitc(self, gp_id: int):
         """Back to the exact mean for the handle's GP ``gp_id`` (gpmpc_gp_fitc with M = 0): what the
         device-side updates ask for first.  Queued on the current stream, no synchronisation."""

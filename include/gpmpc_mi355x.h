@@ -21,6 +21,9 @@
  * outside the rule because they touch nothing of the handle on the device: gpmpc_gp_posterior takes
  * no handle, and gpmpc_preprocess carries its model parameters by value; their buffers are the
  * caller's to order.  (tests/stream_order_util.py lists every stream-taking call under one of the two.)
+ * gpmpc_gp_inducing takes no stream: it is a synchronous builder in the class of gpmpc_gp_reserve, with no
+ * device input of the caller's, and it keeps the rule on a stream the handle owns, which waits for the
+ * handle's event first and carries the record when the call returns, its work completed.
  * The library reads no environment variables: every option is an explicit call.
  */
 #ifndef GPMPC_MI355X_H
@@ -297,6 +300,42 @@ gpmpc_status gpmpc_gp_fitc(gpmpc_handle* h, int32_t gp_id, int32_t M, const int3
  * the weights are copied on `stream`. */
 gpmpc_status gpmpc_get_gp_fitc(gpmpc_handle* h, int32_t gp_id, int32_t* M, int32_t* idx_dev, double* w_dev,
                                void* stream);
+
+/* Choose the FITC inducing rows of GP gp_id on the device, by the kernel instead of a random draw (the
+ * reference's np_random.choice, gpmpc/gpmpc.py:387): up to M of the GP's n training rows, picked greedily by
+ * residual prior variance, which is a pivoted partial Cholesky factorisation of the prior covariance k(X, X)
+ * of the handle's own rows at its current hyperparameters (csrc/gp_observe.hip).  The likelihood noise is not
+ * in it: K_ss has none.
+ *   d_i = outputscale for every live row.  For t = 0 .. M-1: the score s_i = d_i / outputscale of the open
+ *   rows; the pick j_t is the largest finite score above tol, ties to the lower index, and when there is none
+ *   the selection stops with count = t; else l_t[i] = (k(x_i, x_j) - sum_{s<t} l_s[i] l_s[j]) / sqrt(d_j) and
+ *   d_i -= l_t[i]^2 for every live row, and row j closes.
+ * Step 0 is an exact tie (every score is 1.0): the lowest live index is picked.  Inert rows (rejected append
+ * blocks, recognised by the zero on the factor's diagonal) are closed from the start, never picked and in no
+ * sum.  Outputs: idx_dev (device int32 [M]) the picks in pick order, then -1 up to M; gain_dev (device float64
+ * [M], may be NULL) the scores s_j at which they were picked, then NaN; resid_dev (device float64 [n], may be
+ * NULL) the final d_i = outputscale - k(x_i, S) K_ss^-1 k(S, x_i), 0 for an inert row (plus the noise it is
+ * FITC's Gamma_i); count_out (host, may be NULL) the number of picks.  The first k picks and gains of a call
+ * with M are those of a call with M = k, and every output is fixed bit for bit by the inputs (every sum has a
+ * fixed order: 16 parts of fixed extent added as a balanced tree; no atomics).
+ * tol = 0 takes M rows whatever their gain, while a positive pivot is left; below a gain of about 1e-12 the
+ * gains are rounding noise, and so is the order of the picks.  With tol > 0 the diagonal of the Cholesky factor
+ * of K_ss in pick order is sqrt(gain x outputscale), so gpmpc_gp_fitc(idx = the picks, M = count, jitter = 0)
+ * has pivots bounded below by sqrt(tol x outputscale), and near-copies of a picked row are never picked.
+ * THE CALL IS SYNCHRONOUS and takes no stream (see "Streams" above): the host needs count before it can call
+ * gpmpc_gp_fitc.  Its launches, one for the start state and one per pick, run on a stream of the handle's own
+ * behind the handle's last call; the count is read back every 64 picks and nothing more is queued after a
+ * stop, which changes no output.  The output buffers must be idle when the call is made (work queued on them
+ * in the caller's streams is not waited for); they are complete when it returns.  Nothing of the GP changes, and
+ * the call allocates no device memory: the l columns [M][capacity] go into the second factor buffer and the rest
+ * into scratch gpmpc_gp_reserve allocates (the handle's stream, the one the overlapped steps of gpmpc_solve use, is
+ * created on first use).  An installed LOVE root or FITC mean is no obstacle: gpmpc_gp_love_root
+ * and gpmpc_gp_fitc had finished with the second factor buffer when they returned and keep nothing in it.
+ * Refused, with nothing written: M outside 1 .. n, tol negative or not finite, idx_dev NULL (GPMPC_ERR_ARG);
+ * GP not set, set without Linv, a FITC upload (Xv != X), or no gpmpc_gp_reserve since gpmpc_set_gp
+ * (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_gp_inducing(gpmpc_handle* h, int32_t gp_id, int32_t M, double tol, int32_t* idx_dev,
+                               double* gain_dev, double* resid_dev, int32_t* count_out);
 
 /* Training rows of GP gp_id (inert rows included; with a FITC mean installed by gpmpc_gp_fitc still the
  * training rows, not the inducing ones) and its capacity; either may be NULL. */
