@@ -137,10 +137,10 @@ struct FitcLayout {
 // [2][c/16] | their indices [2][c/16] int32 | the rows' state [c] int32 | the state words (gpmpc_common.h kInd*).
 // The l columns go into the second factor buffer.
 struct InducingLayout {
-    size_t c, nb = c / kSelectBlock, d = 0, bval = 2 * c, bidx = bval + 2 * nb, state = bidx + nb,
+    size_t c, nb = c / kPickBlock, d = 0, bval = 2 * c, bidx = bval + 2 * nb, state = bidx + nb,
               flag = state + c / 2, end = flag + kIndInts / 2;
 };
-static_assert(kSelectBlock == 16, "InducingLayout takes its blocks to be the 16 rows a capacity is padded to");
+static_assert(kPickBlock == 16, "InducingLayout takes its blocks to be the 16 rows a capacity is padded to");
 // what it installs: rows [m][4] | tX, tW [m/16][64] each | the indices [m] int32
 struct FitcOut {
     size_t m, rows = 0, tX = 4 * m, tW = 8 * m, idx = 12 * m, end = idx + m / 2;
@@ -157,8 +157,8 @@ struct ObserveLayout {
 struct SelectLayout {
     size_t ldp, nblk, g, vt[kMaxGP], lcol, d, bval, bidx, state, end;
     SelectLayout(size_t b, size_t ngp, const size_t* rows) {
-        ldp = (b + kSelectBlock - 1) / kSelectBlock * kSelectBlock;
-        nblk = ldp / kSelectBlock;
+        ldp = (b + kPickBlock - 1) / kPickBlock * kPickBlock;
+        nblk = ldp / kPickBlock;
         g = ngp;
         size_t at = 0;
         for (size_t q = 0; q < (size_t)kMaxGP; ++q) {
@@ -177,7 +177,7 @@ struct SelectLayout {
 // [g][mcap][ldn] | p [2][g][ldn] | the blocks' best scores [2][nblk] | their indices [2][nblk][2] int32 | the rows'
 // state [ldn] int32
 struct RedundantLayout {
-    size_t ldn, mcap, g, nblk = ldn / kRedundantBlock, ccol = 0, p = g * mcap * ldn, bval = p + 2 * g * ldn,
+    size_t ldn, mcap, g, nblk = ldn / kPickBlock, ccol = 0, p = g * mcap * ldn, bval = p + 2 * g * ldn,
                          bidx = bval + 2 * nblk, state = bidx + 2 * nblk, end = state + ldn / 2;
 };
 constexpr bool layouts_hold(size_t c) {
@@ -1346,7 +1346,7 @@ gpmpc_status gpmpc_gp_inducing(gpmpc_handle* h, int32_t gp_id, int32_t M, double
     a.M = M;
     a.d = h->md.gp_dim[gp_id];
     a.ld = cpad;
-    a.nblk = (n + kSelectBlock - 1) / kSelectBlock;
+    a.nblk = (n + kPickBlock - 1) / kPickBlock;
     a.c = -0.5 * g.inv_ell2;
     a.sf2 = g.sf2;
     a.tol = tol;
@@ -2063,14 +2063,50 @@ static ObserveLayout observe_layout(const gpmpc_handle* h) {
     return ObserveLayout{(size_t)h->max_batch, D, (size_t)h->md.ngp};
 }
 
+// Replaces a scratch buffer of the handle by a fresh one of `doubles` (a synchronous setup step); a failed allocation
+// leaves the handle as it was
+static gpmpc_status replace_scratch(double** buf, size_t doubles) {
+    double* fresh = nullptr;
+    const hipError_t e = hipMalloc(&fresh, doubles * sizeof(double));
+    if (e != hipSuccess) return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    if (*buf) (void)hipFree(*buf);   // (waits for the work queued on it)
+    *buf = fresh;
+    return GPMPC_OK;
+}
+
 // The scratch of gpmpc_gp_informative / gpmpc_gp_observe, allocated by the first call that needs it (a setup step)
 static gpmpc_status ensure_observe_scratch(gpmpc_handle* h) {
-    if (h->obs) return GPMPC_OK;
-    const hipError_t e = hipMalloc(&h->obs, observe_layout(h).end * sizeof(double));
-    if (e != hipSuccess) {
-        h->obs = nullptr;
-        return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    return h->obs ? GPMPC_OK : replace_scratch(&h->obs, observe_layout(h).end);
+}
+
+// The GP inputs of P points, gathered as gpmpc_preprocess gathers them (no targets: x_next is not read), and their
+// variances per GP, gpmpc_gp_predict's variance launch (with_noise = 0) on GP g's columns of the gathered rows: both
+// in the observe scratch, queued on s
+struct PointVariances {
+    const double* Z;      // [P][ldz]
+    int32_t ldz;
+    const double* var;    // [n_gp][ldv]
+    int32_t ldv;
+};
+static gpmpc_status queue_point_variances(gpmpc_handle* h, int32_t P, const double* x_dev, const double* u_dev,
+                                          hipStream_t s, PointVariances* out) {
+    const ObserveLayout lay = observe_layout(h);
+    GPObserve a = observe_args(h, P, x_dev, u_dev, nullptr, P, nullptr, 1.0, 0.0);
+    a.inputs = h->obs + lay.zin;
+    HIPCHK(launch_gp_observe(a, s));
+    for (int g = 0, col = 0; g < h->md.ngp; col += h->md.gp_dim[g], ++g) {
+        PostArgs pa{};
+        pa.Z = h->obs + lay.zin + col;
+        pa.ldz = (int)lay.D;
+        pa.P = P;
+        pa.d = h->md.gp_dim[g];
+        pa.with_noise = 0;
+        pa.var = h->obs + lay.var + (size_t)g * h->max_batch;
+        pa.var_stride = 1;
+        pa.var_off = 0;
+        HIPCHK(launch_gp_post(h->P.gp[g], h->gp[g].npad, pa, false, s, h->var_trim ? 0 : 1));
     }
+    *out = PointVariances{h->obs + lay.zin, (int32_t)lay.D, h->obs + lay.var, h->max_batch};
     return GPMPC_OK;
 }
 
@@ -2106,34 +2142,19 @@ gpmpc_status gpmpc_gp_informative(gpmpc_handle* h, int32_t P, const double* x_de
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(order_after_last(h, s));
     StreamMark mark{h, s};
-    const ObserveLayout lay = observe_layout(h);
-    // the GP inputs of the P points, as gpmpc_preprocess gathers them (no targets: x_next is not read)
-    GPObserve a = observe_args(h, P, x_dev, u_dev, nullptr, P, nullptr, 1.0, 0.0);
-    a.inputs = h->obs + lay.zin;
-    HIPCHK(launch_gp_observe(a, s));
+    PointVariances pv{};
+    const gpmpc_status queued = queue_point_variances(h, P, x_dev, u_dev, s, &pv);
+    if (queued != GPMPC_OK) return queued;
     GPRank r{};
-    r.Z = h->obs + lay.zin;
-    r.ldz = (int)lay.D;
-    r.var = h->obs + lay.var;
-    r.ldv = h->max_batch;
+    r.Z = pv.Z;
+    r.ldz = pv.ldz;
+    r.var = pv.var;
+    r.ldv = pv.ldv;
     r.n_gp = h->md.ngp;
-    for (int g = 0, col = 0; g < h->md.ngp; col += h->md.gp_dim[g], ++g) {
-        // gpmpc_gp_predict's variance launch (with_noise = 0) on GP g's columns of the gathered rows
-        PostArgs pa{};
-        pa.Z = h->obs + lay.zin + col;
-        pa.ldz = (int)lay.D;
-        pa.P = P;
-        pa.d = h->md.gp_dim[g];
-        pa.with_noise = 0;
-        pa.var = h->obs + lay.var + (size_t)g * h->max_batch;
-        pa.var_stride = 1;
-        pa.var_off = 0;
-        HIPCHK(launch_gp_post(h->P.gp[g], h->gp[g].npad, pa, false, s, h->var_trim ? 0 : 1));
-        r.sf2[g] = h->P.gp[g].sf2;
-    }
+    for (int g = 0; g < h->md.ngp; ++g) r.sf2[g] = h->P.gp[g].sf2;
     r.P = P;
     r.m = m;
-    r.score = h->obs + lay.score;
+    r.score = h->obs + observe_layout(h).score;
     r.score_out = score_dev;
     r.pick = pick_dev;
     HIPCHK(launch_gp_score_rank(r, s));
@@ -2141,7 +2162,7 @@ gpmpc_status gpmpc_gp_informative(gpmpc_handle* h, int32_t P, const double* x_de
 }
 
 // The scratch of gpmpc_gp_select: made by the first call and made again when a GP's capacity has grown past what its
-// V region holds (a synchronous setup step).  A failed allocation leaves the handle as it was.
+// V region holds (replace_scratch).
 static gpmpc_status ensure_select_scratch(gpmpc_handle* h) {
     size_t rows[kMaxGP] = {0, 0, 0, 0};
     bool fits = h->sel != nullptr;
@@ -2150,11 +2171,8 @@ static gpmpc_status ensure_select_scratch(gpmpc_handle* h) {
         fits = fits && rows[g] <= h->sel_rows[g];
     }
     if (fits) return GPMPC_OK;
-    double* fresh = nullptr;
-    const hipError_t e = hipMalloc(&fresh, SelectLayout((size_t)h->max_batch, (size_t)h->md.ngp, rows).end * sizeof(double));
-    if (e != hipSuccess) return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    if (h->sel) (void)hipFree(h->sel);   // (waits for the work queued on it)
-    h->sel = fresh;
+    const gpmpc_status got = replace_scratch(&h->sel, SelectLayout((size_t)h->max_batch, (size_t)h->md.ngp, rows).end);
+    if (got != GPMPC_OK) return got;
     for (int g = 0; g < kMaxGP; ++g) h->sel_rows[g] = rows[g];
     return GPMPC_OK;
 }
@@ -2178,33 +2196,22 @@ gpmpc_status gpmpc_gp_select(gpmpc_handle* h, int32_t P, const double* x_dev, co
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(order_after_last(h, s));
     StreamMark mark{h, s};
-    const ObserveLayout lay = observe_layout(h);
     const SelectLayout sl((size_t)h->max_batch, (size_t)h->md.ngp, h->sel_rows);
     // the GP inputs of the P candidates and their start variances: gpmpc_gp_informative's launches
-    GPObserve a = observe_args(h, P, x_dev, u_dev, nullptr, P, nullptr, 1.0, 0.0);
-    a.inputs = h->obs + lay.zin;
-    HIPCHK(launch_gp_observe(a, s));
+    PointVariances pv{};
+    got = queue_point_variances(h, P, x_dev, u_dev, s, &pv);
+    if (got != GPMPC_OK) return got;
     GPSelect q{};
     q.P = P;
     q.m = m;
     q.n_gp = h->md.ngp;
     q.ldp = (int)sl.ldp;
-    q.nblk = (P + kSelectBlock - 1) / kSelectBlock;
-    q.Z = h->obs + lay.zin;
-    q.ldz = (int)lay.D;
-    q.var0 = h->obs + lay.var;
-    q.ldv = h->max_batch;
+    q.nblk = (P + kPickBlock - 1) / kPickBlock;
+    q.Z = pv.Z;
+    q.ldz = pv.ldz;
+    q.var0 = pv.var;
+    q.ldv = pv.ldv;
     for (int g = 0, col = 0; g < h->md.ngp; col += h->md.gp_dim[g], ++g) {
-        PostArgs pa{};
-        pa.Z = h->obs + lay.zin + col;
-        pa.ldz = (int)lay.D;
-        pa.P = P;
-        pa.d = h->md.gp_dim[g];
-        pa.with_noise = 0;
-        pa.var = h->obs + lay.var + (size_t)g * h->max_batch;
-        pa.var_stride = 1;
-        pa.var_off = 0;
-        HIPCHK(launch_gp_post(h->P.gp[g], h->gp[g].npad, pa, false, s, h->var_trim ? 0 : 1));
         const GPDev& gd = h->P.gp[g];
         GPSelectGP& sg = q.g[g];
         sg.rows = gd.vrows;
@@ -2253,15 +2260,11 @@ gpmpc_status gpmpc_gp_redundant(gpmpc_handle* h, int32_t m, int32_t* pick_dev, d
                                        std::to_string(n) + " rows asked for");
     if (m > kRedundantMaxPicks) return fail(GPMPC_ERR_ARG, "m must be at most " + std::to_string(kRedundantMaxPicks));
     (void)hipSetDevice(h->device);
-    // the scratch: made by the first call and made again when a capacity or the picks have grown past it (a
-    // synchronous setup step); a failed allocation leaves the handle as it was
+    // the scratch: made by the first call and made again when a capacity or the picks have grown past it
     if (!h->red || rows > h->red_rows || (size_t)m > h->red_m) {
         const size_t want_rows = std::max(rows, h->red_rows), want_m = std::max(((size_t)m + 15) / 16 * 16, h->red_m);
-        double* fresh = nullptr;
-        const hipError_t e = hipMalloc(&fresh, RedundantLayout{want_rows, want_m, (size_t)ngp}.end * sizeof(double));
-        if (e != hipSuccess) return fail(GPMPC_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-        if (h->red) (void)hipFree(h->red);   // (waits for the work queued on it)
-        h->red = fresh;
+        const gpmpc_status got = replace_scratch(&h->red, RedundantLayout{want_rows, want_m, (size_t)ngp}.end);
+        if (got != GPMPC_OK) return got;
         h->red_rows = want_rows;
         h->red_m = want_m;
     }
@@ -2274,7 +2277,7 @@ gpmpc_status gpmpc_gp_redundant(gpmpc_handle* h, int32_t m, int32_t* pick_dev, d
     q.m = m;
     q.n_gp = ngp;
     q.ldn = (int)lay.ldn;
-    q.nblk = (n + kRedundantBlock - 1) / kRedundantBlock;
+    q.nblk = (n + kPickBlock - 1) / kPickBlock;
     for (int g = 0; g < ngp; ++g) {
         GPRedundantGP& rg = q.g[g];
         rg.linvT = h->P.gp[g].linvT;

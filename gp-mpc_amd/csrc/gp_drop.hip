@@ -43,6 +43,7 @@
 // contents are unspecified (every access stays in bounds whatever the values).
 //
 // The tile pack stays centred on the xbar gpmpc_set_gp computed (tX is moved, tW rewritten).
+#include "gp_pick.h"
 #include "gp_tile.h"
 
 namespace gpmpc {
@@ -513,47 +514,14 @@ hipError_t launch_gp_drop_prep(const GPDropPrep& a, hipStream_t stream) {
 //   c_t[i] = (P_ij - sum_{s<t} c_s[i] c_s[j]) / sqrt(p_j),  p_i -= c_t[i]^2,
 // the pick being the row whose score max_g (1 / p_g,i - sn2_g) / sf2_g is smallest.  A row inert in GP g (a zero on
 // the diagonal of M) has a zero row of linvT: its term is 0 and g is not conditioned on it.
-// One launch per pick, no grid-wide barrier: every workgroup reduces the previous launch's per-block bests to the
-// same j_t, conditions its kRedundantBlock rows and leaves its own best for the next launch; p and the bests are
-// double-buffered by the parity of t.  A workgroup is kRedundantBlock rows times kRedParts parts of the inner
-// product: part q takes the column tiles [q nt / 16, (q + 1) nt / 16) of the two rows and the c columns
-// s = q, q + 16, .., one sequential sum, and the parts are added as a balanced tree.  No atomics.
-constexpr int kRedParts = 16;
-constexpr int kRedThreads = kRedundantBlock * kRedParts;
-constexpr int kRedNone = 0x7fffffff;
-struct RedBest {
-    double val;
-    int idx, nf;   // the smallest finite score's row (kRedNone: none); the lowest row with a non-finite score
-};
-__device__ __forceinline__ RedBest red_merge(const RedBest& x, const RedBest& y) {
-    RedBest r = x;
-    if (y.idx != kRedNone && (x.idx == kRedNone || y.val < x.val || (y.val == x.val && y.idx < x.idx))) {
-        r.val = y.val;
-        r.idx = y.idx;
-    }
-    r.nf = min(x.nf, y.nf);
-    return r;
-}
-__device__ __forceinline__ RedBest red_candidate(double s, int i, bool open) {
-    const bool fin = isfinite(s);
-    return RedBest{(open && fin) ? s : 0.0, (open && fin) ? i : kRedNone, (open && !fin) ? i : kRedNone};
-}
-// over each group of kRedundantBlock consecutive lanes; the group's first lane holds the result
-__device__ __forceinline__ RedBest red_group_best(RedBest b) {
-#pragma unroll
-    for (int off = kRedundantBlock / 2; off >= 1; off >>= 1) {
-        RedBest o;
-        o.val = __shfl_down(b.val, off, kRedundantBlock);
-        o.idx = __shfl_down(b.idx, off, kRedundantBlock);
-        o.nf = __shfl_down(b.nf, off, kRedundantBlock);
-        b = red_merge(b, o);
-    }
-    return b;
-}
+// This is the pick loop of gp_pick.h with the smallest score as the best; p is double-buffered by the parity of t as
+// the bests are.  Part q of the inner product takes the column tiles [q nt / 16, (q + 1) nt / 16) of the two rows
+// and the c columns s = q, q + 16, .. .  No atomics.
+
 // Part kp of linvT[i] . linvT[j] (whole tiles: rows are 128-byte aligned)
 __device__ __forceinline__ double red_dot_part(const GPRedundantGP& g, int i, int j, int kp) {
     const int nt = g.npad / 16;
-    const int q0 = 4 * (kp * nt / kRedParts), q1 = 4 * ((kp + 1) * nt / kRedParts);
+    const int q0 = 4 * (kp * nt / kPickParts), q1 = 4 * ((kp + 1) * nt / kPickParts);
     const double4* ri = reinterpret_cast<const double4*>(g.linvT + (size_t)i * g.npad);
     const double4* rj = reinterpret_cast<const double4*>(g.linvT + (size_t)j * g.npad);
     double acc = 0.0;
@@ -566,17 +534,6 @@ __device__ __forceinline__ double red_dot_part(const GPRedundantGP& g, int i, in
     }
     return acc;
 }
-// the parts of one row, ((0 + 1) + (2 + 3)) + ..
-__device__ __forceinline__ double red_tree(const double (*part)[kRedundantBlock], int ci) {
-    double r[kRedParts];
-#pragma unroll
-    for (int q = 0; q < kRedParts; ++q) r[q] = part[q][ci];
-#pragma unroll
-    for (int w = kRedParts / 2; w >= 1; w >>= 1)
-#pragma unroll
-        for (int q = 0; q < w; ++q) r[q] = r[2 * q] + r[2 * q + 1];
-    return r[0];
-}
 __device__ __forceinline__ bool red_live(const GPRedundantGP& g, int i) { return g.linvT[(size_t)i * g.npad + i] != 0.0; }
 // GP g's term of row i's score, folded into the largest so far (a NaN stays: nothing compares above it)
 __device__ __forceinline__ double red_score(const GPRedundantGP& g, int gi, bool live, double p, double s) {
@@ -585,11 +542,11 @@ __device__ __forceinline__ double red_score(const GPRedundantGP& g, int gi, bool
 }
 
 // The start state: p_g,i = |linvT_g[i]|^2, nothing picked, each block's best, ok = 1
-__global__ __launch_bounds__(kRedThreads) void gp_redundant_init_kernel(const GPRedundant a) {
-    __shared__ double part[kRedParts][kRedundantBlock];
+__global__ __launch_bounds__(kPickThreads) void gp_redundant_init_kernel(const GPRedundant a) {
+    __shared__ double part[kPickParts][kPickBlock];
     const int tid = threadIdx.x;
-    const int ci = tid % kRedundantBlock, kp = tid / kRedundantBlock;
-    const int i = blockIdx.x * kRedundantBlock + ci;
+    const int ci = tid % kPickBlock, kp = tid / kPickBlock;
+    const int i = blockIdx.x * kPickBlock + ci;
     const bool valid = i < a.n;
     const int ii = valid ? i : a.n - 1;
     double score = 0.0;
@@ -598,64 +555,42 @@ __global__ __launch_bounds__(kRedThreads) void gp_redundant_init_kernel(const GP
         part[kp][ci] = red_dot_part(g, ii, ii, kp);
         __syncthreads();
         if (kp == 0 && valid) {
-            const double p = red_tree(part, ci);
+            const double p = pick_tree(part, ci);
             a.p[(size_t)gi * a.ldn + i] = p;
             score = red_score(g, gi, red_live(g, i), p, score);
         }
         __syncthreads();
     }
     if (kp == 0) {
-        RedBest nb{0.0, kRedNone, kRedNone};
+        PickBest nb = pick_none();
         if (valid) {
             a.state[i] = 0;
-            nb = red_candidate(score, i, true);
+            nb = pick_candidate(score, i, true);
         }
-        nb = red_group_best(nb);
-        if (tid == 0) {
-            a.bval[blockIdx.x] = nb.val;
-            a.bidx[2 * blockIdx.x] = nb.idx;
-            a.bidx[2 * blockIdx.x + 1] = nb.nf;
-        }
+        nb = pick_group_best<kPickSmallest>(nb);
+        if (tid == 0) pick_store_best<true>(a.bval, a.bidx, blockIdx.x, nb);
     }
     if (blockIdx.x == 0 && tid == 0 && a.ok != nullptr) a.ok[0] = 1;
 }
 
 // Pick t
-__global__ __launch_bounds__(kRedThreads) void gp_redundant_step_kernel(const GPRedundant a, const int t) {
-    __shared__ double sval[kRedThreads];
-    __shared__ int sidx[kRedThreads], snf[kRedThreads];
-    __shared__ double part[kRedParts][kRedundantBlock];
+__global__ __launch_bounds__(kPickThreads) void gp_redundant_step_kernel(const GPRedundant a, const int t) {
+    __shared__ double sval[kPickThreads];
+    __shared__ int sidx[kPickThreads], snf[kPickThreads];
+    __shared__ double part[kPickParts][kPickBlock];
     const int tid = threadIdx.x;
     const int cur = t & 1, nxt = cur ^ 1;
-    RedBest b{0.0, kRedNone, kRedNone};
-    for (int k = tid; k < a.nblk; k += kRedThreads) {
-        const size_t at = (size_t)cur * a.nblk + k;
-        b = red_merge(b, RedBest{a.bval[at], a.bidx[2 * at], a.bidx[2 * at + 1]});
-    }
-    sval[tid] = b.val;
-    sidx[tid] = b.idx;
-    snf[tid] = b.nf;
-    __syncthreads();
-    for (int s = kRedThreads / 2; s >= 1; s >>= 1) {
-        if (tid < s) {
-            const RedBest r = red_merge(RedBest{sval[tid], sidx[tid], snf[tid]},
-                                        RedBest{sval[tid + s], sidx[tid + s], snf[tid + s]});
-            sval[tid] = r.val;
-            sidx[tid] = r.idx;
-            snf[tid] = r.nf;
-        }
-        __syncthreads();
-    }
-    const bool fin = sidx[0] != kRedNone;   // a finite score is left; else the non-finite ones in index order
-    const int j = fin ? sidx[0] : snf[0];
-    const double sj = sval[0];
+    const PickBest best = pick_reduce_blocks<kPickSmallest, true>(a.bval, a.bidx, a.nblk, cur, sval, sidx, snf);
+    const bool fin = best.idx != kPickNone;   // a finite score is left; else the non-finite ones in index order
+    const int j = fin ? best.idx : best.nf;
+    const double sj = best.val;
     if (j < 0 || j >= a.n) return;   // (m < n leaves a row for every pick; uniform)
     if (blockIdx.x == 0 && tid == 0) {
         a.pick[t] = j;
         if (a.score != nullptr) a.score[t] = fin ? sj : __longlong_as_double(0x7ff8000000000000ll);
     }
-    const int ci = tid % kRedundantBlock, kp = tid / kRedundantBlock;
-    const int i = blockIdx.x * kRedundantBlock + ci;
+    const int ci = tid % kPickBlock, kp = tid / kPickBlock;
+    const int i = blockIdx.x * kPickBlock + ci;
     const bool valid = i < a.n;
     const int ii = valid ? i : a.n - 1;
     const size_t ldn = a.ldn;
@@ -671,10 +606,10 @@ __global__ __launch_bounds__(kRedThreads) void gp_redundant_step_kernel(const GP
         double cv = 0.0;
         if (good) {
             double acc = red_dot_part(g, ii, j, kp);
-            for (int s = kp; s < t; s += kRedParts) acc = fma(-g.ccol[(size_t)s * ldn + ii], g.ccol[(size_t)s * ldn + j], acc);
+            for (int s = kp; s < t; s += kPickParts) acc = fma(-g.ccol[(size_t)s * ldn + ii], g.ccol[(size_t)s * ldn + j], acc);
             part[kp][ci] = acc;
             __syncthreads();
-            if (kp == 0) cv = red_tree(part, ci) / sqrt(pj);
+            if (kp == 0) cv = pick_tree(part, ci) / sqrt(pj);
             __syncthreads();
         }
         if (kp == 0 && valid) {
@@ -684,31 +619,26 @@ __global__ __launch_bounds__(kRedThreads) void gp_redundant_step_kernel(const GP
             score = red_score(g, gi, red_live(g, i), pn, score);
         }
     }
-    if (kp == 0) {   // (the first kRedundantBlock lanes of wave 0)
-        RedBest nb{0.0, kRedNone, kRedNone};
+    if (kp == 0) {   // (the first kPickBlock lanes of wave 0)
+        PickBest nb = pick_none();
         if (valid) {
             int st = a.state[i];
             if (i == j) a.state[i] = st = 1;
-            nb = red_candidate(score, i, st == 0);
+            nb = pick_candidate(score, i, st == 0);
         }
-        nb = red_group_best(nb);
-        if (tid == 0) {
-            const size_t at = (size_t)nxt * a.nblk + blockIdx.x;
-            a.bval[at] = nb.val;
-            a.bidx[2 * at] = nb.idx;
-            a.bidx[2 * at + 1] = nb.nf;
-        }
+        nb = pick_group_best<kPickSmallest>(nb);
+        if (tid == 0) pick_store_best<true>(a.bval, a.bidx, (size_t)nxt * a.nblk + blockIdx.x, nb);
     }
 }
 
 hipError_t launch_gp_redundant(const GPRedundant& a, hipStream_t stream) {
     if (a.n < 2 || a.m < 1 || a.m >= a.n || a.m > kRedundantMaxPicks || a.n > a.ldn || a.n_gp < 1 || a.n_gp > kMaxGP ||
-        a.nblk != (a.n + kRedundantBlock - 1) / kRedundantBlock)
+        a.nblk != (a.n + kPickBlock - 1) / kPickBlock)
         return hipErrorInvalidValue;
     for (int g = 0; g < a.n_gp; ++g)
         if (a.g[g].npad < 16 || a.g[g].npad % 16 != 0 || a.n > a.g[g].npad) return hipErrorInvalidValue;
-    GP_LAUNCH(gp_redundant_init_kernel, dim3(a.nblk), dim3(kRedThreads), stream, a);
-    for (int t = 0; t < a.m; ++t) GP_LAUNCH(gp_redundant_step_kernel, dim3(a.nblk), dim3(kRedThreads), stream, a, t);
+    GP_LAUNCH(gp_redundant_init_kernel, dim3(a.nblk), dim3(kPickThreads), stream, a);
+    for (int t = 0; t < a.m; ++t) GP_LAUNCH(gp_redundant_step_kernel, dim3(a.nblk), dim3(kPickThreads), stream, a, t);
     return hipSuccess;
 }
 

@@ -3,7 +3,8 @@
 // counting rank of the points' variance scores.  One thread per output row; nothing here synchronises the host.
 // Below them the greedy conditional-variance selection (gpmpc_gp_select): the V kernel and the pick loop; and the
 // greedy choice of a GP's FITC inducing rows among its own training rows (gpmpc_gp_inducing): the same pick loop
-// over a grid of the rows, with an end by tolerance.
+// (gp_pick.h) over a grid of the rows, with an end by tolerance.
+#include "gp_pick.h"
 #include "gp_tile.h"
 #include "gpmpc_common.h"
 #include "models.h"
@@ -208,40 +209,6 @@ __global__ __launch_bounds__(64 * kSelWaves) void gp_select_v_kernel(const GPSel
     }
 }
 
-// A block's best candidates: the largest finite score (ties to the lower index; idx INT_MAX: none) and the lowest
-// index among the candidates whose score is not finite (INT_MAX: none).  The order is total, so a reduction gives the
-// same result in whatever order it merges.
-struct SelectBest {
-    double val;
-    int idx, nf;
-};
-constexpr int kSelNone = 0x7fffffff;
-__device__ __forceinline__ SelectBest select_merge(const SelectBest& x, const SelectBest& y) {
-    SelectBest r = x;
-    if (y.idx != kSelNone && (x.idx == kSelNone || y.val > x.val || (y.val == x.val && y.idx < x.idx))) {
-        r.val = y.val;
-        r.idx = y.idx;
-    }
-    r.nf = min(x.nf, y.nf);
-    return r;
-}
-__device__ __forceinline__ SelectBest select_candidate(double s, int i, bool open) {
-    const bool fin = isfinite(s);
-    return SelectBest{(open && fin) ? s : 0.0, (open && fin) ? i : kSelNone, (open && !fin) ? i : kSelNone};
-}
-// over each group of kSelectBlock consecutive lanes; the group's first lane holds the result
-__device__ __forceinline__ SelectBest select_group_best(SelectBest b) {
-#pragma unroll
-    for (int off = kSelectBlock / 2; off >= 1; off >>= 1) {
-        SelectBest o;
-        o.val = __shfl_down(b.val, off, kSelectBlock);
-        o.idx = __shfl_down(b.idx, off, kSelectBlock);
-        o.nf = __shfl_down(b.nf, off, kSelectBlock);
-        b = select_merge(b, o);
-    }
-    return b;
-}
-
 // gp_score_kernel's score of candidate i from the variances d[g * ldd + i]
 __device__ __forceinline__ double select_score(const GPSelect& a, const double* d, size_t ldd, int i, bool bad_input) {
     double s = d[i] / a.g[0].sf2;
@@ -253,74 +220,47 @@ __device__ __forceinline__ double select_score(const GPSelect& a, const double* 
 }
 
 // The start state: d = the variance launches' output, the non-finite inputs marked, each block's best, ok = 1.
-// One wave = 64 / kSelectBlock candidate blocks.
+// One wave = 64 / kPickBlock candidate blocks.
 __global__ __launch_bounds__(64) void gp_select_init_kernel(const GPSelect a) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     const bool valid = i < a.P;
-    SelectBest b{0.0, kSelNone, kSelNone};
+    PickBest b = pick_none();
     if (valid) {
         for (int g = 0; g < a.n_gp; ++g) a.d[(size_t)g * a.ldp + i] = a.var0[(size_t)g * a.ldv + i];
         bool finite = true;
         for (int k = 0; k < a.ldz; ++k) finite = finite && isfinite(a.Z[(size_t)i * a.ldz + k]);
         a.state[i] = finite ? 0 : 2;
-        b = select_candidate(select_score(a, a.var0, a.ldv, i, !finite), i, true);
+        b = pick_candidate(select_score(a, a.var0, a.ldv, i, !finite), i, true);
     }
-    b = select_group_best(b);
-    const int blk = i / kSelectBlock;
-    if (threadIdx.x % kSelectBlock == 0 && blk < a.nblk) {
-        a.bval[blk] = b.val;
-        a.bidx[2 * blk] = b.idx;
-        a.bidx[2 * blk + 1] = b.nf;
-    }
+    b = pick_group_best<kPickLargest>(b);
+    const int blk = i / kPickBlock;
+    if (threadIdx.x % kPickBlock == 0 && blk < a.nblk) pick_store_best<true>(a.bval, a.bidx, blk, b);
     if (i == 0 && a.ok != nullptr) a.ok[0] = 1;
 }
 
-// Pick t.  Every workgroup reduces the blocks' bests of the previous launch to j_t (the same total order everywhere),
-// then conditions its kSelectBlock candidates of every GP on j_t and leaves its own best for the next launch.  A
-// workgroup is kSelectBlock candidates times kSelectParts parts of the inner product
+// Pick t of the pick loop: the workgroup's kPickBlock candidates of every GP conditioned on j_t.  The inner product is
 // v_i . v_j + sum_s l_s[i] l_s[j]: part q takes the column tiles [q nt / 16, (q + 1) nt / 16) of V (nt = npad / 16)
-// and the l columns s = q, q + 16, .., one sequential sum, and the parts are added as a balanced tree,
-// ((0 + 1) + (2 + 3)) + .. .  The split depends on npad and t only, so a candidate's values do not depend on where it
-// sits.  One step reads all of V once: with few candidates per workgroup and the loads of four columns in flight the
-// launch is spread over P / kSelectBlock workgroups instead of waiting on one chain of dependent loads.
-constexpr int kSelectParts = 16;
-constexpr int kSelThreads = kSelectBlock * kSelectParts;
-__global__ __launch_bounds__(kSelThreads) void gp_select_step_kernel(const GPSelect a, const int t) {
-    __shared__ double sval[kSelThreads];
-    __shared__ int sidx[kSelThreads], snf[kSelThreads];
-    __shared__ double part[kSelectParts][kSelectBlock];
+// and the l columns s = q, q + 16, .. .  The split depends on npad and t only.  One step reads all of V once: with few
+// candidates per workgroup and the loads of four columns in flight the launch is spread over P / kPickBlock
+// workgroups instead of waiting on one chain of dependent loads.
+__global__ __launch_bounds__(kPickThreads) void gp_select_step_kernel(const GPSelect a, const int t) {
+    __shared__ double sval[kPickThreads];
+    __shared__ int sidx[kPickThreads], snf[kPickThreads];
+    __shared__ double part[kPickParts][kPickBlock];
     const int tid = threadIdx.x;
     const int cur = t & 1, nxt = cur ^ 1;
-    SelectBest b{0.0, kSelNone, kSelNone};
-    for (int k = tid; k < a.nblk; k += kSelThreads) {
-        const size_t at = (size_t)cur * a.nblk + k;
-        b = select_merge(b, SelectBest{a.bval[at], a.bidx[2 * at], a.bidx[2 * at + 1]});
-    }
-    sval[tid] = b.val;
-    sidx[tid] = b.idx;
-    snf[tid] = b.nf;
-    __syncthreads();
-    for (int s = kSelThreads / 2; s >= 1; s >>= 1) {
-        if (tid < s) {
-            const SelectBest r = select_merge(SelectBest{sval[tid], sidx[tid], snf[tid]},
-                                              SelectBest{sval[tid + s], sidx[tid + s], snf[tid + s]});
-            sval[tid] = r.val;
-            sidx[tid] = r.idx;
-            snf[tid] = r.nf;
-        }
-        __syncthreads();
-    }
-    const bool fin = sidx[0] != kSelNone;   // a finite candidate is left; else the non-finite ones in index order
-    const int j = fin ? sidx[0] : snf[0];
-    const double gain = sval[0];
+    const PickBest best = pick_reduce_blocks<kPickLargest, true>(a.bval, a.bidx, a.nblk, cur, sval, sidx, snf);
+    const bool fin = best.idx != kPickNone;   // a finite candidate is left; else the non-finite ones in index order
+    const int j = fin ? best.idx : best.nf;
+    const double gain = best.val;
     if (j < 0 || j >= a.P) return;   // (m <= P leaves a candidate for every pick; uniform)
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
     if (blockIdx.x == 0 && tid == 0) {
         a.pick[t] = j;
         if (a.gain != nullptr) a.gain[t] = fin ? gain : nan;
     }
-    const int ci = tid % kSelectBlock, kp = tid / kSelectBlock;
-    const int i = blockIdx.x * kSelectBlock + ci;
+    const int ci = tid % kPickBlock, kp = tid / kPickBlock;
+    const int i = blockIdx.x * kPickBlock + ci;
     const bool valid = i < a.P;
     const int ii = valid ? i : a.P - 1;
     const size_t ldp = a.ldp;
@@ -335,7 +275,7 @@ __global__ __launch_bounds__(kSelThreads) void gp_select_step_kernel(const GPSel
         double l = 0.0;
         if (good) {
             const int ntile = g.npad / 16;
-            const int c0 = 16 * (kp * ntile / kSelectParts), c1 = 16 * ((kp + 1) * ntile / kSelectParts);
+            const int c0 = 16 * (kp * ntile / kPickParts), c1 = 16 * ((kp + 1) * ntile / kPickParts);
             const double* vi = g.Vt + ii;
             const double* vj = g.Vt + j;
             double acc = 0.0;
@@ -349,20 +289,13 @@ __global__ __launch_bounds__(kSelThreads) void gp_select_step_kernel(const GPSel
 #pragma unroll
                 for (int k = 0; k < 4; ++k) acc = fma(x[k], y[k], acc);
             }
-            for (int s = kp; s < t; s += kSelectParts)
+            for (int s = kp; s < t; s += kPickParts)
                 acc = fma(g.lcol[(size_t)s * ldp + ii], g.lcol[(size_t)s * ldp + j], acc);
             part[kp][ci] = acc;
             __syncthreads();
             if (kp == 0) {
-                double r[kSelectParts];
-#pragma unroll
-                for (int q = 0; q < kSelectParts; ++q) r[q] = part[q][ci];
-#pragma unroll
-                for (int w = kSelectParts / 2; w >= 1; w >>= 1)
-#pragma unroll
-                    for (int q = 0; q < w; ++q) r[q] = r[2 * q] + r[2 * q + 1];
                 const double k = select_kernel_value(g, a.Z + (size_t)ii * a.ldz + g.zcol, a.Z + (size_t)j * a.ldz + g.zcol);
-                l = (k - r[0]) / sqrt(pv);
+                l = (k - pick_tree(part, ci)) / sqrt(pv);
             }
             __syncthreads();
         }
@@ -375,73 +308,63 @@ __global__ __launch_bounds__(kSelThreads) void gp_select_step_kernel(const GPSel
             if (gi == 0 || sg > score || sg != sg) score = sg;
         }
     }
-    if (kp == 0) {   // (the first kSelectBlock lanes of wave 0)
-        SelectBest nb{0.0, kSelNone, kSelNone};
+    if (kp == 0) {   // (the first kPickBlock lanes of wave 0)
+        PickBest nb = pick_none();
         if (valid) {
             int st = a.state[i];
             if (i == j) a.state[i] = st = st | 1;
-            nb = select_candidate((st & 2) ? nan : score, i, !(st & 1));
+            nb = pick_candidate((st & 2) ? nan : score, i, !(st & 1));
         }
-        nb = select_group_best(nb);
-        if (tid == 0) {
-            const size_t at = (size_t)nxt * a.nblk + blockIdx.x;
-            a.bval[at] = nb.val;
-            a.bidx[2 * at] = nb.idx;
-            a.bidx[2 * at + 1] = nb.nf;
-        }
+        nb = pick_group_best<kPickLargest>(nb);
+        if (tid == 0) pick_store_best<true>(a.bval, a.bidx, (size_t)nxt * a.nblk + blockIdx.x, nb);
     }
 }
 
 // ------------------------------------------------------------------ greedy inducing rows (gpmpc_gp_inducing)
-// The same pivoted Cholesky over a GP's own training rows with the prior covariance: d_i = sf2 at the start, no V, no
-// noise, and an end as soon as no open row's score d_i / sf2 exceeds tol.  The grid runs over the n rows and the
-// history grows to M columns (2000 at the large quad3d size, against gp_select's 256), so what gp_select_step_kernel
-// reads straight from memory inside its sum, the pivot row l_s[j], is staged here: it is a gather over the columns
-// (stride ld), the same for every row of the workgroup, and read from memory inside the sum it doubles the loads of
-// the dependent loop with lines of which 8 bytes are used.  Each chunk of kSelThreads columns is gathered once, one
-// column per thread and all in flight together, into LDS, where the kSelectBlock rows of a part read one address
-// (a broadcast) and a wave's four parts four consecutive ones; the rows' own entries are loaded kSelectParts at a
-// time ahead of their sums.
+// The same pick loop over a GP's own training rows with the prior covariance: d_i = sf2 at the start, no V, no noise,
+// an end as soon as no open row's score d_i / sf2 exceeds tol, and so no use for a row whose score is not finite: the
+// blocks' bests keep one index (kNf = false).  The grid runs over the n rows and the history grows to M columns (2000
+// at the large quad3d size, against gp_select's 256), so what gp_select_step_kernel reads straight from memory inside
+// its sum, the pivot row l_s[j], is staged here: it is a gather over the columns (stride ld), the same for every row
+// of the workgroup, and read from memory inside the sum it doubles the loads of the dependent loop with lines of which
+// 8 bytes are used.  Each chunk of kPickThreads columns is gathered once, one column per thread and all in flight
+// together, into LDS, where the kPickBlock rows of a part read one address (a broadcast) and a wave's four parts four
+// consecutive ones; the rows' own entries are loaded kPickParts at a time ahead of their sums.
 
 // The start state: d = sf2 and open for a live row, 0 and closed for an inert one (a zero on the factor's diagonal),
 // each block's best (every live score is exactly 1: the lowest live index wins), the outputs' tails (-1, NaN) in
-// full, the state words.  One wave = 64 / kSelectBlock row blocks.
+// full, the state words.  One wave = 64 / kPickBlock row blocks.
 __global__ __launch_bounds__(64) void gp_inducing_init_kernel(const GPInducing a) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     const bool valid = i < a.n;
-    SelectBest b{0.0, kSelNone, kSelNone};
+    PickBest b = pick_none();
     if (valid) {
         const bool live = a.linvT[(size_t)i * a.npad + i] != 0.0;
         a.dd[i] = live ? a.sf2 : 0.0;
         a.state[i] = live ? 0 : 3;
-        b = select_candidate(a.sf2 / a.sf2, i, live);
+        b = pick_candidate(a.sf2 / a.sf2, i, live);
         if (i < a.M) {
             a.idx[i] = -1;
             if (a.gain != nullptr) a.gain[i] = __longlong_as_double(0x7ff8000000000000ll);
         }
     }
-    b = select_group_best(b);
-    const int blk = i / kSelectBlock;
-    if (threadIdx.x % kSelectBlock == 0 && blk < a.nblk) {
-        a.bval[blk] = b.val;
-        a.bidx[blk] = b.idx;
-    }
+    b = pick_group_best<kPickLargest>(b);
+    const int blk = i / kPickBlock;
+    if (threadIdx.x % kPickBlock == 0 && blk < a.nblk) pick_store_best<false>(a.bval, a.bidx, blk, b);
     if (i == 0) {
         a.flag[kIndStop] = 0;
         a.flag[kIndCount] = -1;
     }
 }
 
-// Pick t.  Every workgroup reduces the blocks' bests of the previous launch to j_t, as gp_select_step_kernel does;
-// when the selection has stopped, or stops here (no open row with a finite score above tol), it leaves the stop for
-// the next launch, the count and the residuals, and returns, uniformly.  Otherwise its kSelectBlock rows times
-// kSelectParts parts form l_t: part q sums the columns s = q, q + 16, .. in order, the parts are added as a balanced
-// tree, ((0 + 1) + (2 + 3)) + .., so a row's values do not depend on where it sits.
-__global__ __launch_bounds__(kSelThreads) void gp_inducing_step_kernel(const GPInducing a, const int t) {
-    __shared__ double sval[kSelThreads];
-    __shared__ int sidx[kSelThreads];
-    __shared__ double lj[kSelThreads];
-    __shared__ double part[kSelectParts][kSelectBlock];
+// Pick t.  When the selection has stopped, or stops here (no open row with a finite score above tol), the workgroup
+// leaves the stop for the next launch, the count and the residuals, and returns, uniformly.  Otherwise its rows form
+// l_t: part q sums the columns s = q, q + 16, .. in order.
+__global__ __launch_bounds__(kPickThreads) void gp_inducing_step_kernel(const GPInducing a, const int t) {
+    __shared__ double sval[kPickThreads];
+    __shared__ int sidx[kPickThreads];
+    __shared__ double lj[kPickThreads];
+    __shared__ double part[kPickParts][kPickBlock];
     const int tid = threadIdx.x;
     const int cur = t & 1, nxt = cur ^ 1;
     const bool first = blockIdx.x == 0 && tid == 0;
@@ -449,27 +372,11 @@ __global__ __launch_bounds__(kSelThreads) void gp_inducing_step_kernel(const GPI
         if (first) a.flag[kIndStop + nxt] = 1;
         return;
     }
-    SelectBest b{0.0, kSelNone, kSelNone};
-    for (int k = tid; k < a.nblk; k += kSelThreads) {
-        const size_t at = (size_t)cur * a.nblk + k;
-        b = select_merge(b, SelectBest{a.bval[at], a.bidx[at], kSelNone});
-    }
-    sval[tid] = b.val;
-    sidx[tid] = b.idx;
-    __syncthreads();
-    for (int s = kSelThreads / 2; s >= 1; s >>= 1) {
-        if (tid < s) {
-            const SelectBest r = select_merge(SelectBest{sval[tid], sidx[tid], kSelNone},
-                                              SelectBest{sval[tid + s], sidx[tid + s], kSelNone});
-            sval[tid] = r.val;
-            sidx[tid] = r.idx;
-        }
-        __syncthreads();
-    }
-    const int j = sidx[0];
-    const double gain = sval[0];
-    const int ci = tid % kSelectBlock, kp = tid / kSelectBlock;
-    const int i = blockIdx.x * kSelectBlock + ci;
+    const PickBest best = pick_reduce_blocks<kPickLargest, false>(a.bval, a.bidx, a.nblk, cur, sval, sidx, nullptr);
+    const int j = best.idx;
+    const double gain = best.val;
+    const int ci = tid % kPickBlock, kp = tid / kPickBlock;
+    const int i = blockIdx.x * kPickBlock + ci;
     const bool valid = i < a.n;
     const int ii = valid ? i : a.n - 1;
     const size_t ld = a.ld;
@@ -491,51 +398,41 @@ __global__ __launch_bounds__(kSelThreads) void gp_inducing_step_kernel(const GPI
     }
     const double pv = din[j];   // (= gain sf2 > 0)
     double acc = 0.0;
-    for (int s0 = 0; s0 < t; s0 += kSelThreads) {
-        const int cnt = min(kSelThreads, t - s0);
+    for (int s0 = 0; s0 < t; s0 += kPickThreads) {
+        const int cnt = min(kPickThreads, t - s0);
         __syncthreads();   // the previous chunk has been read
         lj[tid] = tid < cnt ? a.lcol[(size_t)(s0 + tid) * ld + j] : 0.0;
-        double x[kSelectParts];
+        double x[kPickParts];
 #pragma unroll
-        for (int k = 0; k < kSelectParts; ++k) {
-            const int q = kp + kSelectParts * k;
+        for (int k = 0; k < kPickParts; ++k) {
+            const int q = kp + kPickParts * k;
             x[k] = q < cnt ? a.lcol[(size_t)(s0 + q) * ld + ii] : 0.0;
         }
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < kSelectParts; ++k) {
-            const int q = kp + kSelectParts * k;
+        for (int k = 0; k < kPickParts; ++k) {
+            const int q = kp + kPickParts * k;
             if (q < cnt) acc = fma(x[k], lj[q], acc);
         }
     }
     part[kp][ci] = acc;
     __syncthreads();
-    if (kp == 0) {   // (the first kSelectBlock lanes of wave 0)
-        SelectBest nb{0.0, kSelNone, kSelNone};
+    if (kp == 0) {   // (the first kPickBlock lanes of wave 0)
+        PickBest nb = pick_none();
         if (valid) {
-            double r[kSelectParts];
-#pragma unroll
-            for (int q = 0; q < kSelectParts; ++q) r[q] = part[q][ci];
-#pragma unroll
-            for (int w = kSelectParts / 2; w >= 1; w >>= 1)
-#pragma unroll
-                for (int q = 0; q < w; ++q) r[q] = r[2 * q] + r[2 * q + 1];
+            const double r = pick_tree(part, ci);
             int st = a.state[i];
             const double k = select_rbf(a.d, a.c, a.sf2, a.rows + (size_t)i * 4, a.rows + (size_t)j * 4);
-            const double l = (st & 2) ? 0.0 : (k - r[0]) / sqrt(pv);
+            const double l = (st & 2) ? 0.0 : (k - r) / sqrt(pv);
             a.lcol[(size_t)t * ld + i] = l;
             const double dn = din[i] - l * l;
             dout[i] = dn;
             if (a.resid != nullptr && t == a.M - 1) a.resid[i] = dn;
             if (i == j) a.state[i] = st = st | 1;
-            nb = select_candidate(dn / a.sf2, i, !(st & 1));
+            nb = pick_candidate(dn / a.sf2, i, !(st & 1));
         }
-        nb = select_group_best(nb);
-        if (tid == 0) {
-            const size_t at = (size_t)nxt * a.nblk + blockIdx.x;
-            a.bval[at] = nb.val;
-            a.bidx[at] = nb.idx;
-        }
+        nb = pick_group_best<kPickLargest>(nb);
+        if (tid == 0) pick_store_best<false>(a.bval, a.bidx, (size_t)nxt * a.nblk + blockIdx.x, nb);
     }
 }
 
@@ -543,7 +440,7 @@ __global__ __launch_bounds__(kSelThreads) void gp_inducing_step_kernel(const GPI
 
 static bool inducing_args_ok(const GPInducing& a) {
     return a.n >= 1 && a.M >= 1 && a.M <= a.n && a.n <= a.ld && a.n <= a.npad && a.npad >= 16 && a.npad % 16 == 0 &&
-           a.nblk == (a.n + kSelectBlock - 1) / kSelectBlock && a.d >= 1 && a.d <= 3 && a.idx != nullptr;
+           a.nblk == (a.n + kPickBlock - 1) / kPickBlock && a.d >= 1 && a.d <= 3 && a.idx != nullptr;
 }
 
 hipError_t launch_gp_inducing_begin(const GPInducing& a, hipStream_t stream) {
@@ -554,19 +451,19 @@ hipError_t launch_gp_inducing_begin(const GPInducing& a, hipStream_t stream) {
 
 hipError_t launch_gp_inducing_step(const GPInducing& a, int t, hipStream_t stream) {
     if (!inducing_args_ok(a) || t < 0 || t >= a.M) return hipErrorInvalidValue;
-    GP_LAUNCH(gp_inducing_step_kernel, dim3(a.nblk), dim3(kSelThreads), stream, a, t);
+    GP_LAUNCH(gp_inducing_step_kernel, dim3(a.nblk), dim3(kPickThreads), stream, a, t);
     return hipSuccess;
 }
 
 hipError_t launch_gp_select(const GPSelect& a, hipStream_t stream) {
     if (a.P < 1 || a.m < 1 || a.m > a.P || a.m > kSelectMaxPicks || a.P > a.ldp || a.n_gp < 1 || a.n_gp > kMaxGP ||
-        a.nblk != (a.P + kSelectBlock - 1) / kSelectBlock)
+        a.nblk != (a.P + kPickBlock - 1) / kPickBlock)
         return hipErrorInvalidValue;
     for (int g = 0; g < a.n_gp; ++g)
         if (a.g[g].npad < 16 || a.g[g].npad % 16 != 0 || a.g[g].nv > a.g[g].npad) return hipErrorInvalidValue;
     GP_LAUNCH(gp_select_v_kernel, dim3((a.P + 16 * kSelWaves - 1) / (16 * kSelWaves), a.n_gp), dim3(64 * kSelWaves), stream, a);
     GP_LAUNCH(gp_select_init_kernel, dim3((a.P + 63) / 64), dim3(64), stream, a);
-    for (int t = 0; t < a.m; ++t) GP_LAUNCH(gp_select_step_kernel, dim3(a.nblk), dim3(kSelThreads), stream, a, t);
+    for (int t = 0; t < a.m; ++t) GP_LAUNCH(gp_select_step_kernel, dim3(a.nblk), dim3(kPickThreads), stream, a, t);
     return hipSuccess;
 }
 

@@ -343,10 +343,12 @@ struct GPDropPrep {
     int32_t* acc;
 };
 
+// Rows per workgroup of the pick loop that GPRedundant, GPSelect and GPInducing below run (gp_pick.h): the unit of
+// their nblk and of the scratch layouts capi.hip carves for them
+constexpr int kPickBlock = 16;
 // Greedy backward selection of the m rows the GPs would miss least (gp_drop.hip; gpmpc_gp_redundant fills it): a
 // pivoted partial Cholesky of the precisions P_g = M_g^T M_g, whose entries are inner products of rows of linvT.
 constexpr int kRedundantMaxPicks = 256;
-constexpr int kRedundantBlock = 16;   // rows per workgroup of the pick loop
 struct GPRedundantGP {
     const double* linvT;  // [npad][npad]
     double* ccol;         // [m][ldn]: c_t[i]
@@ -356,7 +358,7 @@ struct GPRedundantGP {
 struct GPRedundant {
     int32_t n, m, n_gp;
     int32_t ldn;          // stride of the per-row arrays (>= n)
-    int32_t nblk;         // ceil(n / kRedundantBlock)
+    int32_t nblk;         // ceil(n / kPickBlock)
     GPRedundantGP g[kMaxGP];
     double* p;            // [2][n_gp][ldn]: step t reads half t & 1 and writes the other
     int32_t* state;       // [ldn]: 1 picked
@@ -527,7 +529,6 @@ hipError_t launch_gp_score_rank(const GPRank& a, hipStream_t stream);
 // scratch of the handle.  Candidate i's entries of V, of the l columns and of d lie at [.][i] with stride ldp, so the
 // pick loop reads them coalesced over the candidates.
 constexpr int kSelectMaxPicks = 256;
-constexpr int kSelectBlock = 16;      // candidates per workgroup of the pick loop
 struct GPSelectGP {
     const double* rows;   // GPDev::vrows [>= npad][4]
     const double* linvT;  // [npad][npad]
@@ -540,7 +541,7 @@ struct GPSelectGP {
 struct GPSelect {
     int32_t P, m, n_gp;
     int32_t ldp;          // stride of the per-candidate arrays (>= P)
-    int32_t nblk;         // ceil(P / kSelectBlock)
+    int32_t nblk;         // ceil(P / kPickBlock)
     const double* Z;      // [P][ldz] the candidates' gathered GP inputs
     int32_t ldz;
     const double* var0;   // [n_gp][ldv]
@@ -567,7 +568,7 @@ struct GPInducing {
     double* lcol;         // [M][ld]: l_t[i] (the second factor buffer)
     int32_t npad, n, M, d;
     int32_t ld;           // the padded capacity: stride of the l columns and of d
-    int32_t nblk;         // ceil(n / kSelectBlock)
+    int32_t nblk;         // ceil(n / kPickBlock)
     double c, sf2, tol;   // c = -1 / (2 ell^2)
     double* dd;           // [2][ld]: step t reads half t & 1 and writes the other
     int32_t* state;       // [ld]: bit 0 closed (picked or inert), bit 1 inert

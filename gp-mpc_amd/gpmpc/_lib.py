@@ -21,7 +21,8 @@ LIB_PATH = Path(os.environ.get("GPMPC_LIB", _DEFAULT_LIB))
 CSRC = Path(__file__).resolve().parents[1] / "csrc"
 # the files gpmpc_build_id's source hash covers, in the Makefile's order (HASHED)
 HASHED = ["sqp_kernel.hip", "gp_kernels.hip", "gp_append.hip", "gp_drop.hip", "gp_refactor.hip", "gp_fit.hip",
-          "gp_love.hip", "gp_fitc.hip", "gp_observe.hip", "capi.hip", "gpmpc_common.h", "gp_tile.h", "models.h", "../../include/gpmpc_mi355x.h", "build_id.cpp", "Makefile"]
+          "gp_love.hip", "gp_fitc.hip", "gp_observe.hip", "capi.hip", "gpmpc_common.h", "gp_tile.h", "gp_pick.h",
+          "models.h", "../../include/gpmpc_mi355x.h", "build_id.cpp", "Makefile"]
 
 _lib = None
 

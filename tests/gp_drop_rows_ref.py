@@ -41,6 +41,7 @@ import numpy as np
 import gp_append_ref as A
 import gp_drop_ref as D
 import gp_ref as R
+from gp_pick_ref import PARTS, tree
 
 LD = R.LD
 SF2, SN2 = D.SF2, D.SN2
@@ -152,7 +153,6 @@ def drop_rows(state, idx, info=None):
 RED_CASES = [(21, 5), (40, 17), (64, 33), (272, 16)]
 # the GPU test's: n = 24, 40, 272 with m = 1, 17, min(n - 1, 33); picks are prefixes, so the longest run serves all
 GPU_RED_CASES = [(24, 23), (40, 33), (272, 33)]
-PARTS = 16
 
 
 def structural_tie(n, m, t):
@@ -170,25 +170,18 @@ def linvT_padded(M):
     return out
 
 
-def _dots(LT, j):
-    """linvT[i] . linvT[j] for every row i, in the kernel's order: 16 parts of whole column tiles, each one
-    sequential sum, added as a balanced tree."""
+def _dots(LT, j=None):
+    """The parts of linvT[i] . linvT[j] for every row i (j = None: of every row against itself), in the kernel's
+    order: part q is one sequential sum over whole column tiles."""
     npad = LT.shape[0]
     nt = npad // 16
     parts = []
     for q in range(PARTS):
         acc = np.zeros(npad)
         for c in range(16 * (q * nt // PARTS), 16 * ((q + 1) * nt // PARTS)):
-            acc = acc + LT[:, c] * LT[j, c]
+            acc = acc + LT[:, c] * (LT[:, c] if j is None else LT[j, c])
         parts.append(acc)
     return parts
-
-
-def _tree(parts):
-    parts = list(parts)
-    while len(parts) > 1:
-        parts = [parts[2 * q] + parts[2 * q + 1] for q in range(len(parts) // 2)]
-    return parts[0]
 
 
 def _scores(p, live, hyp):
@@ -217,15 +210,7 @@ def redundant_f64(Ms, hyp, m):
     n = Ms[0].shape[0]
     LTs = [linvT_padded(M) for M in Ms]
     live = [np.diag(M) != 0.0 for M in Ms]
-    p = []
-    for LT in LTs:
-        nt, parts = LT.shape[0] // 16, []
-        for q in range(PARTS):   # every row against itself: the same parts and tree
-            acc = np.zeros(LT.shape[0])
-            for c in range(16 * (q * nt // PARTS), 16 * ((q + 1) * nt // PARTS)):
-                acc = acc + LT[:, c] * LT[:, c]
-            parts.append(acc)
-        p.append(_tree(parts)[:n].copy())
+    p = [tree(_dots(LT))[:n].copy() for LT in LTs]   # every row against itself: the same parts and tree
     cols = [np.zeros((m, n)) for _ in Ms]
     open_ = np.ones(n, dtype=bool)
     picks, scores, tables, ok = [], [], [], 1
@@ -245,7 +230,7 @@ def redundant_f64(Ms, hyp, m):
             parts = [q[:n].copy() for q in _dots(LT, j)]
             for s_ in range(t):
                 parts[s_ % PARTS] = parts[s_ % PARTS] - cols[g][s_] * cols[g][s_, j]
-            c = _tree(parts) / math.sqrt(pj)
+            c = tree(parts) / math.sqrt(pj)
             cols[g][t] = c
             p[g] = p[g] - c * c
         open_[j] = False

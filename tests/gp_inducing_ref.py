@@ -46,6 +46,7 @@ import numpy as np
 import gp_drop_ref as D
 import gp_ref as R
 import gp_select_ref as S
+from gp_pick_ref import PARTS, tree
 
 LD = R.LD
 R_MODEL = 2.12
@@ -54,7 +55,6 @@ GAP_FACTOR = S.GAP_FACTOR
 SF2 = S.SF2
 NS = S.NS                  # 24 (a ragged tile), 40, 272 (more than 16 row blocks, t past 32)
 TOL = 1e-4
-PARTS = 16                 # parts of the pick loop's inner product (csrc/gp_observe.hip kSelectParts)
 # tol = 0: the m up to which the picks are comparable, per GP (GP 0's gains are rounding noise by step 16)
 M_TOL0 = ((1, 6), (1, 17, 33))
 # the ordering test: GP 0's lengthscale times this before the selection (the picks must differ)
@@ -142,10 +142,8 @@ def greedy_f64(X, ell, sf2, M, tol, live=None):
             for c in range(q, t, PARTS):
                 acc = acc + ls[c] * ls[c][j]
             parts.append(acc)
-        while len(parts) > 1:   # the balanced tree ((0 + 1) + (2 + 3)) + ..
-            parts = [parts[2 * q] + parts[2 * q + 1] for q in range(len(parts) // 2)]
         k = D.kernel64(X[j:j + 1], ell, sf2, X)[:, 0]
-        l = np.where(live, (k - parts[0]) / math.sqrt(d[j]), 0.0)
+        l = np.where(live, (k - tree(parts)) / math.sqrt(d[j]), 0.0)
         ls.append(l)
         d = d - l * l
         open_[j] = False

@@ -50,6 +50,7 @@ import gp_append_ref as A
 import gp_drop_ref as D
 import gp_ref as R
 import observe_ref as OR
+from gp_pick_ref import PARTS, tree
 
 LD = R.LD
 R_MODEL = 2.66
@@ -60,7 +61,6 @@ DUP, NANROW = (3, 7), 5    # transition 7 repeats transition 3; transition 5 hol
 SF2 = (2.5, 0.7)           # outputscales that are not 1
 NS, PS = (24, 40, 272), (1, 40, 130)
 CLUSTERS, COPIES = 8, 16
-PARTS = 16                 # parts of the pick loop's inner product (csrc/gp_observe.hip kSelectParts)
 
 
 def ms_for(P):
@@ -215,10 +215,8 @@ def greedy_f64(gps, Zs, m):
             for s in range(q, t, PARTS):
                 acc = acc + ls[s] * ls[s][j]
             parts.append(acc)
-        while len(parts) > 1:   # the balanced tree ((0 + 1) + (2 + 3)) + ..
-            parts = [parts[2 * q] + parts[2 * q + 1] for q in range(len(parts) // 2)]
         k = D.kernel64(Zc[g][j:j + 1], gp["ell"], gp["sf2"], Zc[g])[:, 0]
-        return k - parts[0]
+        return k - tree(parts)
 
     picks, gains, ds, _, ok = _greedy(ds, [gp["sf2"] for gp in gps], [gp["sn2"] for gp in gps], finite, m, column)
     return dict(picks=picks, gains=gains.astype(np.float64), resid=np.stack(ds), ok=ok, finite=finite)
