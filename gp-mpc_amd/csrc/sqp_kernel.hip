@@ -45,6 +45,9 @@
 #ifndef GPMPC_PHASE_LANE   // (round-6 A/B of phase_lane: 0 off, 1 one-wave and quad3d kernels, 2 every kernel)
 #define GPMPC_PHASE_LANE 1
 #endif
+#ifndef GPMPC_LANE_PLAN   // 1: the factorisation takes the case analysis of its per-lane streams from compile-time lane masks (LanePlan), one-wave single-tile kernels with the split IPM layout (H + 1 <= 32); 2: every one-wave single-tile kernel (A/B variants: 0 = evaluated from the lane at every entry)
+#define GPMPC_LANE_PLAN 1
+#endif
 
 namespace gpmpc {
 
@@ -311,6 +314,131 @@ __device__ __attribute__((noinline)) void gp_tiles_dispatch(const double* tX, co
     }
 }
 
+// ------------------------------------------------------------------ lane plans (GPMPC_LANE_PLAN)
+// The Newton-solve phases of the single-tile kernels (NX + 1 <= 8, NU <= 2) address LDS through per-lane
+// streams: a base and a stride per operand, masked lanes on the zero / dummy slots with stride 0.  Which
+// stream a lane takes, and at which offset inside a stage, depends on the lane and on the model alone.
+// The functions below state that per stream (sel 0: masked, off = slot of the zero block; otherwise the
+// stream's base, off = doubles past it), in the case-by-case form the phases used to evaluate at every
+// entry (compares, mask logic and exec-mask branches: most of their set-up).  Since the cases are known
+// per model at compile time, the one-wave kernels take them as constants instead (GPMPC_LANE_PLAN): the
+// lanes of a selector are a 64-bit literal (sel_mask, applied with one v_cndmask), and the offset is
+// formed without case analysis (sel_off, valid on the selected lanes).  Nothing is held in registers or
+// LDS between phases.  consistent() checks the two forms against each other for all 64 lanes (the
+// kernels without the plan keep their own case-by-case text in mfma_backward_h, which fac_* restate).
+struct PlanStream {
+    int sel, off;
+};
+template <int NX, int NU>
+struct LanePlan {
+    static constexpr int NB = NX + NU, GS = NB + 1, PS = NX + 1, PO = NX * (NX + 1) / 2, CI = NX, UI = 8;
+    static constexpr __host__ __device__ int pidx(int i, int j) { return i * NX - (i * (i - 1)) / 2 + (j - i); }   // i <= j < NX
+    // homogeneous 16-wide tile index -> G' column (-1: structurally zero) and stage variable (-1: none)
+    static constexpr __host__ __device__ int gcol(int t) { return t < NX ? t : (t == CI ? NB : ((t >= UI && t < UI + NU) ? NX + t - UI : -1)); }
+    static constexpr __host__ __device__ int svar(int t) { return t < NX ? t : ((t >= UI && t < UI + NU) ? NX + t - UI : -1); }
+
+    // ---- factorisation (v_mfma_f64_16x16x4: lr = lane >> 4, lc = lane & 15)
+    // G'' row 4 s + lr, column lc (base G'_k; sel 2: the affine column CI): the zero block's one slot for
+    // the homogeneous corner
+    static constexpr __host__ __device__ PlanStream fac_g(int lane, int s) {
+        const int lr = lane >> 4, lc = lane & 15, t = lr + 4 * s;
+        const bool ld = t < NX && gcol(lc) >= 0;
+        const bool one = t == CI && lc == CI;
+        return ld ? PlanStream{lc == CI ? 2 : 1, t * GS + gcol(lc)} : PlanStream{0, one ? 7 : 0};
+    }
+    // C-init of M', row lr + 4 r: sel 1 = hq_k (the diagonal), sel 2 = gq_k (column CI), sel 3 = gq_k (row CI)
+    static constexpr __host__ __device__ PlanStream fac_d(int lane, int r) {
+        const int lr = lane >> 4, lc = lane & 15, t = lr + 4 * r;
+        if (svar(t) >= 0 && t == lc) return {1, svar(t)};
+        if (svar(t) >= 0 && lc == CI) return {2, svar(t)};
+        if (t == CI && svar(lc) >= 0) return {3, svar(lc)};
+        return {0, 0};
+    }
+    // P'_H, row lr + 4 r (r < 2): diag(hq_H[x]), gq_H[x] in row and column CI, selectors as fac_d
+    static constexpr __host__ __device__ PlanStream fac_init(int lane, int r) {
+        const int lr = lane >> 4, lc = lane & 15, t = lr + 4 * r;
+        if (t < NX && lc < NX) return t == lc ? PlanStream{1, t} : PlanStream{0, 0};
+        if (t < NX && lc == CI) return {2, t};
+        if (t == CI && lc < NX) return {3, lc};
+        return {0, 0};
+    }
+    // store of P'_k, row lr + 4 r (r < 2), into the packed block (base P'_k): upper triangle (sel 1) and p (sel 2)
+    static constexpr __host__ __device__ PlanStream fac_p(int lane, int r) {
+        const int lr = lane >> 4, lc = lane & 15, t = lr + 4 * r;
+        const bool st = t < NX && ((lc == CI) || (lc < NX && t <= lc));
+        const int idx = (lc == CI) ? PO + t : pidx(t < lc ? t : lc, t < lc ? lc : t);
+        return st ? PlanStream{lc == CI ? 2 : 1, idx} : PlanStream{0, 0};
+    }
+    // store of K'_k = [K (sel 1) | kff (sel 2)] (base K'_k) and of Ru_k^-1 (base Ru_k^-1)
+    static constexpr __host__ __device__ PlanStream fac_k(int lane) {
+        const int lr = lane >> 4, lc = lane & 15;
+        const bool st = lr < NU && (lc < NX || lc == CI);
+        return st ? PlanStream{lc == CI ? 2 : 1, lr * PS + (lc == CI ? NX : lc)} : PlanStream{0, 0};
+    }
+    static constexpr __host__ __device__ PlanStream fac_r(int lane) { return lane < NU * NU ? PlanStream{1, lane} : PlanStream{0, 0}; }
+
+    // ---- the plan: per stream, the lanes of each selector as a 64-bit constant, and the offset in a form
+    // that holds on the selected lanes only (no case analysis: the masks have done it)
+    enum Id { kG, kD, kInit, kP, kK, kR, kIds };
+    static constexpr __host__ __device__ int count(int id) { return id == kD ? 3 : ((id == kG || id == kInit || id == kP) ? 2 : 1); }
+    static constexpr __host__ __device__ PlanStream stream(int id, int lane, int i) {
+        switch (id) {
+            case kG: return fac_g(lane, i);
+            case kD: return fac_d(lane, i);
+            case kInit: return fac_init(lane, i);
+            case kP: return fac_p(lane, i);
+            case kK: return fac_k(lane);
+            default: return fac_r(lane);
+        }
+    }
+    // lanes whose stream (id, i) has selector sel; lanes that are masked onto the one slot (zero + 7)
+    static constexpr __host__ __device__ uint64_t sel_mask(int id, int i, int sel) {
+        uint64_t m = 0;
+        for (int l = 0; l < 64; ++l) m |= (uint64_t)(stream(id, l, i).sel == sel) << l;
+        return m;
+    }
+    static constexpr __host__ __device__ uint64_t one_mask(int id, int i) {
+        uint64_t m = 0;
+        for (int l = 0; l < 64; ++l) m |= (uint64_t)(stream(id, l, i).sel == 0 && stream(id, l, i).off == 7) << l;
+        return m;
+    }
+    // offset of stream (id, i) on the lanes with selector sel >= 1 (any value elsewhere)
+    static constexpr __host__ __device__ uint64_t row_table() {   // pidx(t, t) - t, one byte per row t < NX
+        static_assert(NX <= 8 && NX * (NX + 1) / 2 < 256, "row bases fit a byte each");
+        uint64_t m = 0;
+        for (int t = 0; t < NX; ++t) m |= (uint64_t)(pidx(t, t) - t) << (8 * t);   // 0 <= pidx(t, t) - t < PO for t < NX
+        return m;
+    }
+    static constexpr __host__ __device__ int sel_off(int id, int lane, int i, int sel) {
+        const int lr = lane >> 4, lc = lane & 15, t = lr + 4 * i;
+        const int sv_lc = lc - ((lane >> 3) & 1) * (UI - NX);
+        switch (id) {
+            case kG: return t * GS + (sel == 1 ? sv_lc : NB);
+            case kD:
+            case kInit: return sel == 3 ? sv_lc : t - (i == 2 ? UI - NX : 0);
+            case kP: return sel == 1 ? (int)((row_table() >> (8 * t)) & 0xff) + lc : PO + t;
+            case kK: return lr * PS + (sel == 1 ? lc : NX);
+            default: return lane;
+        }
+    }
+    // the masks and sel_off give every lane the stream the functions above state: selectors 0..3, masked
+    // lanes on slot 0 or 7; and P'_H (kInit) is the C-init stream of its row wherever it is not zero
+    static constexpr __host__ __device__ bool consistent() {
+        for (int id = 0; id < kIds; ++id)
+            for (int i = 0; i < count(id); ++i)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const PlanStream st = stream(id, lane, i);
+                    if (st.sel < 0 || st.sel > 3) return false;
+                    if (st.sel == 0 && st.off != 0 && st.off != 7) return false;
+                    if (st.sel != 0 && sel_off(id, lane, i, st.sel) != st.off) return false;
+                    if (id == kInit && st.sel != 0 && (fac_d(lane, i).sel != st.sel || fac_d(lane, i).off != st.off)) return false;
+                }
+        return true;
+    }
+};
+static_assert(LanePlan<Model<kQuad2D>::NX, Model<kQuad2D>::NU>::consistent(), "quad2d: the lane plan reproduces every stream");
+static_assert(LanePlan<Model<kCartpole>::NX, Model<kCartpole>::NU>::consistent(), "cartpole: the lane plan reproduces every stream");
+
 // Waves per instance: the wide model (quad3d) always runs four (its LDS allows one instance per CU);
 // the single-tile models run one, or two / four when the batch leaves SIMDs idle (launch_sqp_step).
 template <int ID>
@@ -363,6 +491,8 @@ struct SqpKernel {
     // the multi-wave MFMA kernels without segments measured 0.5 % slower with it (their scratch frame
     // grew by 80-160 B/lane); the segment path and quad3d's two-tile path keep the full re-solve too.
     static constexpr bool kCorrDelta = GPMPC_CORR_DELTA != 0 && kMfma && !SEG && NW == 1;
+    // lane plans of the Newton-solve phases (plan_stream below)
+    static constexpr bool kLanePlan = GPMPC_LANE_PLAN != 0 && kMfma && !SEG && NW == 1;
     static constexpr int LI = 8 + NU;
     static_assert(!SEG || LI + NX <= 16, "lambda slots in the 16-wide tile");
     static constexpr int KST = SEG ? 2 * NX + 1 : PS;          // K' row stride
@@ -850,62 +980,118 @@ struct SqpKernel {
     // The u rows sit at 8..8+NU-1 = lane groups 0..NU-1 of element 2: the Schur A operand needs no
     // lane move.  Stores of stage k are issued after stage k-1's W' products (sched_barrier), off
     // the chain.  Outputs: packed P', K' = [K | kff], Ru^-1 per stage.
+    // PLAN: the lane's streams from LanePlan's masks (the default: wherever the kernel has them, so a
+    // caller that names no form, such as tools/ric_micro.hip, runs what the one-wave kernels run)
+    template <bool PLAN = kLanePlan>
     __device__ static bool mfma_backward_h(const Lds& L, int H, int lane) {
         lane = phase_lane(lane);
         const int lr = lane >> 4, lc = lane & 15;
         constexpr int CI = NX, UI = 8;
         static_assert(NX + 1 <= 8 && NU <= 2 && UI + NU <= 16, "homogeneous tile layout");
-        // tile index -> G' column (-1: structurally zero) and stage variable (-1: none)
-        auto gcol = [](int t) { return t < NX ? t : (t == CI ? NB : ((t >= UI && t < UI + NU) ? NX + t - UI : -1)); };
-        auto svar = [](int t) { return t < NX ? t : ((t >= UI && t < UI + NU) ? NX + t - UI : -1); };
-        const int gc_lc = gcol(lc), sv_lc = svar(lc);
-        double pn[2];
+        // per-lane (base, stride) streams of stages H-1 .. 0; masked lanes on the zero / dummy slots, stride 0
+        double pn[2];          // P'_H: diag(hq_H[x]), gq_H[x] in row and column CI
+        const double* pg[2];   // G'' rows 4s + lr (K index), column lc
+        int gst[2];
+        const double* pd[3];   // C-init of M' (rows lr + 4r, r = 0..2): hq on the diagonal, gq in row and column CI
+        int dst[3];
+        double* sp[2];         // stores: P'_k (packed), K'_k, Ru_k^-1
+        int sp_st[2];
+        double *sk, *srui;
+        int sk_st, srui_st;
+        if constexpr (PLAN) {
+            // the case analysis from LanePlan's lane masks (plan_stream)
+            using LP = LanePlan<NX, NU>;
+            static_for<2>([&](auto s2) {
+                const PlanStream g = plan_stream<LP::kG, decltype(s2)::value>(lane);
+                pg[s2] = (g.sel ? L.G + (size_t)(H - 1) * NX * GS : L.zero) + g.off;
+                gst[s2] = g.sel ? NX * GS : 0;
+            });
+            static_for<3>([&](auto r) {
+                const PlanStream d = plan_stream<LP::kD, decltype(r)::value>(lane);
+                const double* base = d.sel == 1 ? L.hq : L.gq;
+                pd[r] = d.sel ? base + (size_t)(H - 1) * NBS + d.off : L.zero;
+                dst[r] = d.sel ? NBS : 0;
+            });
+            static_for<2>([&](auto r) {
+                // where P'_H is not zero, it is the C-init stream of its row one stage up (LanePlan::consistent)
+                const PlanStream in = plan_stream<LP::kInit, decltype(r)::value>(lane);
+                pn[r] = *(in.sel ? pd[r] + NBS : L.zero);
+                const PlanStream p = plan_stream<LP::kP, decltype(r)::value>(lane);
+                sp[r] = p.sel ? L.P + (size_t)(H - 1) * PP + p.off : L.dummy;
+                sp_st[r] = p.sel ? PP : 0;
+                sp[r][sp_st[r]] = pn[r];   // P'_H (packed) for the multiplier recovery of stage H-1
+            });
+            const PlanStream ks = plan_stream<LP::kK>(lane);
+            sk = ks.sel ? L.K + (size_t)(H - 1) * NU * PS + ks.off : L.dummy;
+            sk_st = ks.sel ? NU * PS : 0;
+            const PlanStream rs = plan_stream<LP::kR>(lane);
+            srui = rs.sel ? L.Rui + (size_t)(H - 1) * NU * NU + rs.off : L.dummy;
+            srui_st = rs.sel ? NU * NU : 0;
+        } else {
+            // evaluated from the lane, case by case: the text the kernels without the plan have always
+            // run.  LanePlan::fac_* restate it per stream (with LanePlan's gcol / svar, used here too); the
+            // static_assert pins the masks to that restatement, and the restatement is tied to this text
+            // by the bit-for-bit runs of both forms (profiles/r21/dump_cmp.txt), not at compile time.
+            using LP = LanePlan<NX, NU>;
+            const int gc_lc = LP::gcol(lc), sv_lc = LP::svar(lc);
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {   // P'_H: diag(hq_H[x]), gq_H[x] in row and column CI
-            const int t = lr + 4 * r;
-            double v = 0.0;
-            if (t < NX && lc < NX) v = (t == lc) ? L.hq[H * NBS + t] : 0.0;
-            else if (t < NX && lc == CI) v = L.gq[H * NBS + t];
-            else if (t == CI && lc < NX) v = L.gq[H * NBS + lc];
-            pn[r] = v;
-        }
-        {   // P'_H (packed) for the multiplier recovery of stage H-1
-            double* PH = L.P + (size_t)H * PP;
+            for (int r = 0; r < 2; ++r) {   // P'_H: diag(hq_H[x]), gq_H[x] in row and column CI
+                const int t = lr + 4 * r;
+                double v = 0.0;
+                if (t < NX && lc < NX) v = (t == lc) ? L.hq[H * NBS + t] : 0.0;
+                else if (t < NX && lc == CI) v = L.gq[H * NBS + t];
+                else if (t == CI && lc < NX) v = L.gq[H * NBS + lc];
+                pn[r] = v;
+            }
+            {   // P'_H (packed) for the multiplier recovery of stage H-1
+                double* PH = L.P + (size_t)H * PP;
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    const int t = lr + 4 * r;
+                    if (t < NX) {
+                        if (lc == CI) PH[PO + t] = pn[r];
+                        else if (lc < NX && t <= lc) PH[pidx(t, lc)] = pn[r];
+                    }
+                }
+            }
+            // G'' rows 4s + lr (K index), column lc: per-lane (base, stride) streams
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                const int t = lr + 4 * s2;
+                const bool ld = t < NX && gc_lc >= 0;
+                const bool one = t == CI && lc == CI;
+                pg[s2] = ld ? L.G + (size_t)(H - 1) * NX * GS + t * GS + gc_lc : L.zero + (one ? 7 : 0);
+                gst[s2] = ld ? NX * GS : 0;
+            }
+            // C-init of M' (rows lr + 4r, r = 0..2): hq on the diagonal, gq in row and column CI
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const int t = lr + 4 * r, sv_t = LP::svar(t);
+                const double* base = L.zero;
+                bool on = false;
+                if (sv_t >= 0 && t == lc) { base = L.hq + sv_t; on = true; }
+                else if (sv_t >= 0 && lc == CI) { base = L.gq + sv_t; on = true; }
+                else if (t == CI && sv_lc >= 0) { base = L.gq + sv_lc; on = true; }
+                pd[r] = on ? base + (size_t)(H - 1) * NBS : L.zero;
+                dst[r] = on ? NBS : 0;
+            }
+            // store streams (stages H-1 .. 0), dummy slot with stride 0 for entries not stored
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
                 const int t = lr + 4 * r;
-                if (t < NX) {
-                    if (lc == CI) PH[PO + t] = pn[r];
-                    else if (lc < NX && t <= lc) PH[pidx(t, lc)] = pn[r];
-                }
+                const bool st = t < NX && ((lc == CI) || (lc < NX && t <= lc));
+                const int idx = (lc == CI) ? PO + t : pidx(t < lc ? t : lc, t < lc ? lc : t);
+                sp[r] = st ? L.P + (size_t)(H - 1) * PP + idx : L.dummy;
+                sp_st[r] = st ? PP : 0;
             }
+            const bool kst = lr < NU && (lc < NX || lc == CI);
+            sk = kst ? L.K + (size_t)(H - 1) * NU * PS + lr * PS + (lc == CI ? NX : lc) : L.dummy;
+            sk_st = kst ? NU * PS : 0;
+            const bool rst = lane < NU * NU;
+            srui = rst ? L.Rui + (size_t)(H - 1) * NU * NU + lane : L.dummy;
+            srui_st = rst ? NU * NU : 0;
         }
         bool ok = true;
-        // G'' rows 4s + lr (K index), column lc: per-lane (base, stride) streams
-        const double* pg[2];
-        int gst[2];
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const int t = lr + 4 * s2;
-            const bool ld = t < NX && gc_lc >= 0;
-            const bool one = t == CI && lc == CI;
-            pg[s2] = ld ? L.G + (size_t)(H - 1) * NX * GS + t * GS + gc_lc : L.zero + (one ? 7 : 0);
-            gst[s2] = ld ? NX * GS : 0;
-        }
-        // C-init of M' (rows lr + 4r, r = 0..2): hq on the diagonal, gq in row and column CI
-        const double* pd[3];
-        int dst[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int t = lr + 4 * r, sv_t = svar(t);
-            const double* base = L.zero;
-            bool on = false;
-            if (sv_t >= 0 && t == lc) { base = L.hq + sv_t; on = true; }
-            else if (sv_t >= 0 && lc == CI) { base = L.gq + sv_t; on = true; }
-            else if (t == CI && sv_lc >= 0) { base = L.gq + sv_lc; on = true; }
-            pd[r] = on ? base + (size_t)(H - 1) * NBS : L.zero;
-            dst[r] = on ? NBS : 0;
-        }
         struct Stage { double g[2], d[3]; };
         auto load_stage = [&](Stage& st) {
 #pragma unroll
@@ -919,23 +1105,6 @@ struct SqpKernel {
                 pd[q] -= dst[q];
             }
         };
-        // store streams (stages H-1 .. 0), dummy slot with stride 0 for entries not stored
-        double* sp[2];
-        int sp_st[2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int t = lr + 4 * r;
-            const bool st = t < NX && ((lc == CI) || (lc < NX && t <= lc));
-            const int idx = (lc == CI) ? PO + t : pidx(t < lc ? t : lc, t < lc ? lc : t);
-            sp[r] = st ? L.P + (size_t)(H - 1) * PP + idx : L.dummy;
-            sp_st[r] = st ? PP : 0;
-        }
-        const bool kst = lr < NU && (lc < NX || lc == CI);
-        double* sk = kst ? L.K + (size_t)(H - 1) * NU * PS + lr * PS + (lc == CI ? NX : lc) : L.dummy;
-        const int sk_st = kst ? NU * PS : 0;
-        const bool rst = lane < NU * NU;
-        double* srui = rst ? L.Rui + (size_t)(H - 1) * NU * NU + lane : L.dummy;
-        const int srui_st = rst ? NU * NU : 0;
         double pend_p[2] = {0.0, 0.0}, pend_k = 0.0, pend_r = 0.0;
         auto flush = [&]() {
 #pragma unroll
@@ -1520,13 +1689,35 @@ struct SqpKernel {
     __host__ __device__ static int seg_start(int w, int H) { return (w * H) / NSEG; }
     __device__ static int lam_of(int t) { return (t >= LI && t < LI + NX) ? t - LI : -1; }
     // Every Newton-solve phase starts from an opaque copy of its lane index, so the lane-derived LDS
-    // addresses of the phase are recomputed there (a few VALU operations) instead of hoisted out of the
-    // SQP loop, held across the IPM and spilled to AGPRs / scratch (reloaded with a memory latency per
-    // phase).  Round 6: the quad2d / cartpole kernels' scratch 112-208 B/lane -> 0.
+    // addresses of the phase are recomputed there instead of hoisted out of the SQP loop, held across
+    // the IPM and spilled to AGPRs / scratch (reloaded with a memory latency per phase).  Round 6: the
+    // quad2d / cartpole kernels' scratch 112-208 B/lane -> 0.  The recomputation is not small: in the
+    // headline kernel's ISA 393 instructions ahead of the factorisation's first MFMA (none of them f64),
+    // 81 ahead of the predictor's forward sweep, 116 and 89 ahead of the corrector's backward and forward
+    // sweeps, per IPM iteration; most of the factorisation's were case analysis on the lane, which
+    // LanePlan now supplies as constants (168 left).
     __device__ static int phase_lane(int lane) {
         if constexpr (GPMPC_PHASE_LANE == 2 || (GPMPC_PHASE_LANE == 1 && (NWAVES == 1 || !kMfma)))
             asm volatile("" : "+v"(lane));
         return lane;
+    }
+    // Lane plans (GPMPC_LANE_PLAN, one-wave single-tile kernels): most of what phase_lane makes a phase
+    // recompute is case analysis on the lane (which stream, or the zero / dummy slot).  plan_stream takes
+    // the cases from LanePlan's compile-time lane masks (an inverse ballot of a literal: two s_mov and the
+    // v_cndmask that uses it) and the offset from LanePlan::sel_off; nothing is carried between phases.
+    // The other kernels keep the case-by-case set-up evaluated from their lane (mfma_backward_h<false>).
+    __device__ static bool lane_bit(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+    template <int STR, int I = 0>
+    __device__ static PlanStream plan_stream(int lane) {
+        using LP = LanePlan<NX, NU>;
+        constexpr uint64_t m1 = LP::sel_mask(STR, I, 1), m2 = LP::sel_mask(STR, I, 2), m3 = LP::sel_mask(STR, I, 3),
+                           mo = LP::one_mask(STR, I);
+        PlanStream st{0, 0};
+        if constexpr (mo != 0) st.off = lane_bit(mo) ? 7 : 0;
+        if constexpr (m3 != 0) st = lane_bit(m3) ? PlanStream{3, LP::sel_off(STR, lane, I, 3)} : st;
+        if constexpr (m2 != 0) st = lane_bit(m2) ? PlanStream{2, LP::sel_off(STR, lane, I, 2)} : st;
+        if constexpr (m1 != 0) st = lane_bit(m1) ? PlanStream{1, LP::sel_off(STR, lane, I, 1)} : st;
+        return st;
     }
     // P_x,lambda of stage k of a lambda segment (in its P' block)
     __device__ static double* pxl_at(const Lds& L, int k) { return L.P + (size_t)k * PPB + PXL; }
@@ -2837,7 +3028,7 @@ struct SqpKernel {
                 } else if constexpr (kMfma) {
                     bool rok = true;
                     if (wv == 0) {   // (WSPL: the other waves wait at the status exchange)
-                        rok = mfma_backward_h(L, H, lane);
+                        rok = mfma_backward_h<kLanePlan && (SPL || GPMPC_LANE_PLAN == 2)>(L, H, lane);
                         WSYNC();
                         TPHASE(8);
                         if (rok) acl_phase<true>(L, H, lane);

@@ -7,16 +7,20 @@ NAME=$1; DEFS=$2
 cd "$(dirname "$0")/../gp-mpc_amd/csrc"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -mllvm -amdgpu-mfma-vgpr-form=1"
 mkdir -p build/v_$NAME ../gpmpc/lib
+SRCS=$(sed -n 's/^SRCS *+\{0,1\}= *//p' Makefile | tr '\n' ' ' | sed 's/\.hip//g')   # the Makefile's SRCS, in its order
+[ -n "$SRCS" ] || { echo "no SRCS in the Makefile" >&2; exit 1; }
 TS=("")
 [ -n "${TIMING_TOO:-}" ] && TS=("" timing)   # TIMING_TOO=1: also the phase-stamp build
 for t in "${TS[@]}"; do
   T=""; [ "$t" = timing ] && T="-DGPMPC_TIMING"
-  for s in sqp_kernel gp_kernels gp_append gp_drop capi; do
+  OBJS=()
+  for s in $SRCS; do
     /opt/rocm/bin/hipcc $F $DEFS $T -c $s.hip -o build/v_$NAME/${s}${t}.o &
+    OBJS+=(build/v_$NAME/${s}${t}.o)
   done
   wait
   /opt/rocm/bin/hipcc -O2 -fPIC -DGPMPC_SRC_HASH="\"variant\"" -DGPMPC_GIT_HEAD="\"$(git rev-parse --short=12 HEAD)\"" \
       -DGPMPC_BUILD_KIND="\"variant-$NAME${t:+-$t} $DEFS\"" -c build_id.cpp -o build/v_$NAME/build_id${t}.o
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ../gpmpc/lib/libgpmpc_mi355x_${NAME}${t:+_$t}.so \
-      build/v_$NAME/sqp_kernel${t}.o build/v_$NAME/gp_kernels${t}.o build/v_$NAME/gp_append${t}.o build/v_$NAME/gp_drop${t}.o build/v_$NAME/capi${t}.o build/v_$NAME/build_id${t}.o
+      "${OBJS[@]}" build/v_$NAME/build_id${t}.o
 done
