@@ -228,6 +228,8 @@ struct gpmpc_handle {
     int32_t* scratch_i = nullptr;   // [2][max_batch]
     double* scratch_d = nullptr;    // [max_batch][4]
     double* obs = nullptr;          // scratch of gpmpc_gp_informative / gpmpc_gp_observe (ObserveLayout), on first use
+    double* roll = nullptr;         // scratch of gpmpc_rollout: the gathered variance inputs [P T][sum d_g], kept for a
+    size_t roll_doubles = 0;        // later call of the same or a smaller size
     double* sel = nullptr;          // scratch of gpmpc_gp_select (SelectLayout), on first use and when a capacity has grown
     size_t sel_rows[kMaxGP] = {0, 0, 0, 0};   // the padded rows its V regions were sized for
     double* red = nullptr;          // scratch of gpmpc_gp_redundant (RedundantLayout), on first use and when a capacity has grown
@@ -391,6 +393,7 @@ static void free_handle(gpmpc_handle* h) {
     if (h->scratch_i) (void)hipFree(h->scratch_i);
     if (h->scratch_d) (void)hipFree(h->scratch_d);
     if (h->obs) (void)hipFree(h->obs);
+    if (h->roll) (void)hipFree(h->roll);
     if (h->sel) (void)hipFree(h->sel);
     if (h->red) (void)hipFree(h->red);
     for (GPSlot& gs : h->gp) (void)gs.release(GPSlot::kBuffers);
@@ -2358,6 +2361,74 @@ gpmpc_status gpmpc_gp_observe(gpmpc_handle* h, int32_t P, const double* x_dev, c
                                                 accepted_dev ? accepted_dev + (size_t)g * ablk : nullptr, stream);
         if (st != GPMPC_OK) return st;
     }
+    return GPMPC_OK;
+}
+
+
+gpmpc_status gpmpc_rollout(gpmpc_handle* h, int32_t P, int32_t T, const double* x0_dev, const double* u_dev,
+                           int32_t with_gp, double* x_dev, double* var_dev) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    const char* bad = nullptr;
+    if (P < 1 || T < 1) bad = "no trajectories or no steps (P, T >= 1)";
+    else if (!x0_dev || !u_dev || !x_dev) bad = "null array (x0_dev, u_dev and x_dev are required)";
+    else if (with_gp != 0 && with_gp != 1) bad = "with_gp must be 0 or 1";
+    else if ((int64_t)P * ((int64_t)T + 1) * h->md.nx > INT32_MAX) bad = "P (T + 1) nx does not fit an int32";
+    if (bad) return fail(GPMPC_ERR_ARG, bad);
+    if (!h->model_set) return fail(GPMPC_ERR_STATE, "the prior parameters are not set (gpmpc_set_model first)");
+    const int ngp = h->md.ngp;
+    if (with_gp) {
+        if (!h->P.use_gp) return fail(GPMPC_ERR_STATE, "with_gp = 1 while the handle's GPs are off (gpmpc_use_gp)");
+        for (int g = 0; g < ngp; ++g)
+            if (!h->gp[g].set) return fail(GPMPC_ERR_STATE, "GP " + std::to_string(g) + " not set");
+    }
+    if (var_dev)
+        for (int g = 0; g < ngp; ++g) {
+            if (!h->gp[g].set) return fail(GPMPC_ERR_STATE, "the variance needs GP " + std::to_string(g) + ", which is not set");
+            if (!h->gp[g].linvT) return fail(GPMPC_ERR_STATE, "the variance needs Linv (GP " + std::to_string(g) + " has none)");
+        }
+    (void)hipSetDevice(h->device);
+    size_t D = 0;
+    for (int g = 0; g < ngp; ++g) D += h->md.gp_dim[g];
+    const size_t need = var_dev ? (size_t)P * T * D : 0;
+    if (need > h->roll_doubles) {   // (before anything is queued: a failed allocation leaves the handle as it was)
+        const gpmpc_status got = replace_scratch(&h->roll, need);
+        if (got != GPMPC_OK) return got;
+        h->roll_doubles = need;
+    }
+    // on a stream of the handle's own, behind the handle's last call, and drained before the call returns
+    HIPCHK(ensure_side(h));
+    hipStream_t s = h->side;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    RolloutArgs a{};
+    for (int i = 0; i < kMaxParams; ++i) a.params[i] = h->P.params[i];
+    a.dt = h->P.dt;
+    a.P = P;
+    a.T = T;
+    a.x0 = x0_dev;
+    a.u = u_dev;
+    a.x = x_dev;
+    if (with_gp)   // the means as the solver reads them: the tile pack of ProblemDev::gp (a FITC overlay included)
+        for (int g = 0; g < ngp; ++g) a.gp[g] = h->P.gp[g];
+    HIPCHK(launch_rollout(h->model, a, with_gp != 0, s));
+    if (var_dev) {
+        // gpmpc_gp_predict's variance launch (with_noise = 0) on GP g's columns of the gathered inputs, written
+        // straight into the caller's [P][T][n_gp]
+        HIPCHK(launch_rollout_inputs(h->model, x_dev, u_dev, P, T, h->roll, s));
+        for (int g = 0, col = 0; g < ngp; col += h->md.gp_dim[g], ++g) {
+            PostArgs pa{};
+            pa.Z = h->roll + col;
+            pa.ldz = (int)D;
+            pa.P = P * T;
+            pa.d = h->md.gp_dim[g];
+            pa.with_noise = 0;
+            pa.var = var_dev;
+            pa.var_stride = ngp;
+            pa.var_off = g;
+            HIPCHK(launch_gp_post(h->P.gp[g], h->gp[g].npad, pa, false, s, h->var_trim ? 0 : 1));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(s));
     return GPMPC_OK;
 }
 

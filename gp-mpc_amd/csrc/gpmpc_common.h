@@ -625,6 +625,20 @@ int model_unc_dims(int model, int32_t* unc);   // the model's uncertain state di
 hipError_t launch_stage_cost(const ProblemDev& P, const double* x, const double* u, const int32_t* tstep,
                              const int32_t* status, double* cost, int B, hipStream_t stream);
 hipError_t launch_gp_mean_grad(const GPDev& g, const double* Z, int P, double* mean, double* grad, hipStream_t stream);
+// An open-loop rollout of the model (sqp_kernel.hip rollout_kernel; gpmpc_rollout fills it), by value like the plant's
+// parameters: P trajectories of T steps from x0 under u.  gp[] is read by the GP variant only.
+struct RolloutArgs {
+    double params[kMaxParams];   // the prior's (ProblemDev::params)
+    double dt;
+    int32_t P, T;                // P (T + 1) nx fits an int32
+    const double* x0;            // [P][nx]
+    const double* u;             // [P][T][nu]
+    double* x;                   // [P][T+1][nx]
+    GPDev gp[kMaxGP];
+};
+hipError_t launch_rollout(int model, const RolloutArgs& a, bool with_gp, hipStream_t stream);
+// Z [P T][D]: the GP inputs z_k[gp_src_g] along x [P][T+1][nx], u [P][T][nu], D = sum of the GPs' dimensions
+hipError_t launch_rollout_inputs(int model, const double* x, const double* u, int P, int T, double* Z, hipStream_t stream);
 hipError_t launch_gp_post(const GPDev& g, int npad, const PostArgs& a, bool from_state, hipStream_t stream,
                           int var_full = 0);   // PostBatch::var_full
 hipError_t launch_gp_post_batch(const PostBatch& pb, bool from_state, hipStream_t stream);

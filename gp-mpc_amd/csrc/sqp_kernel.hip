@@ -3928,6 +3928,153 @@ hipError_t launch_gp_mean_grad(const GPDev& g, const double* Z, int P, double* m
     return hipGetLastError();
 }
 
+// Open-loop rollout of the model over T steps (gpmpc_rollout): x_{k+1} = RK4(f_prior + res(GP means))(x_k, u_k), the
+// discrete map of the SQP's multiple-shooting constraint (gpmpc/gpmpc.py:204-209 the RK4 of the build, :171-199 the
+// residual dynamics), the steps in sequence inside one launch.
+//   GP = true:  one wavefront per 16 trajectories, the evaluation tile of gp_tiles<1>.  Lane l integrates trajectory
+//               l & 15 of its tile (the four 16-lane rows hold the same values, so no result crosses lanes but the
+//               tile sums); lanes 0..15 touch memory.  Per RK4 substage the row-0 lanes write {z - xbar, 1} and
+//               c|z - xbar|^2 of every GP due to LDS (gp_mean_grad_kernel's layout), the wave runs the tile sums once
+//               per GP, and every lane reads its mean sf2 S0 back.  A GP whose input is a control (gp_state_dep false)
+//               is constant over the step: evaluated at substage 0 only.  Column z of both MFMA products depends on
+//               point z alone, so a trajectory's bits do not depend on its neighbours, its slot or the batch.
+//   GP = false: the means are the constant zero plant_step_kernel passes, one lane per trajectory, 64 per wavefront;
+//               the arithmetic is plant_step_kernel's, statement by statement, so the states are its bits.
+// A padding lane (p >= P) of a GP tile repeats the last trajectory and stores nothing.
+template <int ID, bool GP>
+__global__ __launch_bounds__(64) void rollout_kernel(RolloutArgs a) {
+    using M = Model<ID>;
+    constexpr int NX = M::NX, NU = M::NU, NGP = M::NGP;
+    constexpr int PER = GP ? 16 : 64;
+    __shared__ double zb[GP ? NGP * 16 * 4 : 1], czz[GP ? NGP * 16 : 1], out[GP ? NGP * 16 * 4 : 1];
+    const int lane = threadIdx.x;
+    const int p = blockIdx.x * PER + (GP ? (lane & 15) : lane);
+    if (!GP && p >= a.P) return;
+    const bool store = p < a.P && (!GP || lane < 16);
+    const size_t tr = (size_t)min(p, a.P - 1);
+    const double* u = a.u + tr * a.T * NU;
+    double* x = a.x + tr * (a.T + 1) * NX;
+    double pv[kMaxParams];
+#pragma unroll
+    for (int i = 0; i < kMaxParams; ++i) pv[i] = a.params[i];
+    const double dt = a.dt;
+    double xs[NX], us[NU], k[NX], acc[NX], xi[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xs[i] = a.x0[tr * NX + i];
+    if (store) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) x[i] = xs[i];
+    }
+    const double cs[4] = {0.0, 0.5, 0.5, 1.0}, ws[4] = {1.0, 2.0, 2.0, 1.0};
+    for (int step = 0; step < a.T; ++step) {
+#pragma unroll
+        for (int c = 0; c < NU; ++c) us[c] = u[(size_t)step * NU + c];
+        double gm[kMaxGP] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) xi[i] = (s == 0) ? xs[i] : fma(cs[s] * dt, k[i], xs[i]);
+            if constexpr (GP) {
+                static_for<NGP>([&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    if (s > 0 && !M::gp_state_dep[G]) return;
+                    const GPDev& g = a.gp[G];
+                    double zc[3];
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        const int src = M::gp_src[G][d];
+                        zc[d] = d < M::gp_dim[G] ? (src < NX ? xi[src] : us[src - NX]) - g.xbar[d] : 0.0;
+                    }
+                    if (lane < 16) {
+                        double* dst = zb + (G * 16 + lane) * 4;
+                        dst[0] = zc[0];
+                        dst[1] = zc[1];
+                        dst[2] = zc[2];
+                        dst[3] = 1.0;
+                        czz[G * 16 + lane] = -0.5 * g.inv_ell2 * fma(zc[0], zc[0], fma(zc[1], zc[1], zc[2] * zc[2]));
+                    }
+                });
+                __syncthreads();
+                static_for<NGP>([&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    if (s > 0 && !M::gp_state_dep[G]) return;
+                    const GPDev& g = a.gp[G];
+                    gp_tiles_dispatch(g.tX, g.tW, g.ntile, zb + G * 64, czz + G * 16, out + G * 64, lane, 1);
+                });
+                __syncthreads();
+                static_for<NGP>([&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    if (s > 0 && !M::gp_state_dep[G]) return;
+                    gm[G] = a.gp[G].sf2 * out[(G * 16 + (lane & 15)) * 4];
+                });
+            }
+            M::f(pv, xi, us, gm, k);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) acc[i] = (s == 0) ? k[i] : fma(ws[s], k[i], acc[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < NX; ++i) xs[i] = fma(dt / 6.0, acc[i], xs[i]);
+        if (store) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) x[(size_t)(step + 1) * NX + i] = xs[i];
+        }
+    }
+}
+
+template <int ID>
+static hipError_t launch_rollout_of(const RolloutArgs& a, bool with_gp, hipStream_t stream) {
+    if (with_gp)
+        hipLaunchKernelGGL((rollout_kernel<ID, true>), dim3((a.P + 15) / 16), dim3(64), 0, stream, a);
+    else
+        hipLaunchKernelGGL((rollout_kernel<ID, false>), dim3((a.P + 63) / 64), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_rollout(int model, const RolloutArgs& a, bool with_gp, hipStream_t stream) {
+    switch (model) {
+        case kQuad2D: return launch_rollout_of<kQuad2D>(a, with_gp, stream);
+        case kQuad3D: return launch_rollout_of<kQuad3D>(a, with_gp, stream);
+        case kCartpole: return launch_rollout_of<kCartpole>(a, with_gp, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+// The GP inputs along a rollout, gathered for the variance launches: Z[p T + k][.] = z_k[gp_src_g] of trajectory p,
+// z_k = [x_k; u_k], the GPs' columns side by side (D = sum of their dimensions).
+template <int ID>
+__global__ __launch_bounds__(256) void rollout_inputs_kernel(const double* __restrict__ x, const double* __restrict__ u,
+                                                             int P, int T, double* __restrict__ Z) {
+    using M = Model<ID>;
+    constexpr int NX = M::NX, NU = M::NU, NGP = M::NGP;
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= (size_t)P * T) return;
+    const size_t p = q / T, kk = q - p * T;
+    const double* xr = x + (p * (T + 1) + kk) * NX;
+    const double* ur = u + q * NU;
+    int D = 0;
+#pragma unroll
+    for (int g = 0; g < NGP; ++g) D += M::gp_dim[g];
+    int col = 0;
+#pragma unroll
+    for (int g = 0; g < NGP; ++g)
+#pragma unroll
+        for (int d = 0; d < M::gp_dim[g]; ++d) {
+            const int src = M::gp_src[g][d];
+            Z[q * D + col++] = src < NX ? xr[src] : ur[src - NX];
+        }
+}
+
+hipError_t launch_rollout_inputs(int model, const double* x, const double* u, int P, int T, double* Z, hipStream_t stream) {
+    const unsigned blocks = (unsigned)(((size_t)P * T + 255) / 256);
+    switch (model) {
+        case kQuad2D: hipLaunchKernelGGL(rollout_inputs_kernel<kQuad2D>, dim3(blocks), dim3(256), 0, stream, x, u, P, T, Z); break;
+        case kQuad3D: hipLaunchKernelGGL(rollout_inputs_kernel<kQuad3D>, dim3(blocks), dim3(256), 0, stream, x, u, P, T, Z); break;
+        case kCartpole: hipLaunchKernelGGL(rollout_inputs_kernel<kCartpole>, dim3(blocks), dim3(256), 0, stream, x, u, P, T, Z); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 // LINEAR_LS stage costs of the stored solution (gpmpc_set_cost_buffer), one thread per (instance,
 // stage), queued right behind the SQP launch: cost[b][k] = 1/2 ||y_k - y_ref,k||^2_W, y = [x; u],
 // W = dt blkdiag(Q, R) on stages 0..H-1 and Q on stage H (gpmpc.py:231-239, mpc.py:101-102, acados

@@ -63,6 +63,7 @@ SIGNATURES = {
     "gpmpc_gp_mean_grad": (_I, [_P, _I, _P, _I, _P, _P, _P]),
     "gpmpc_gp_posterior": (_I, [_I, _I, _I, _P, _P, _D, _D, _D, _P, _I, _P, _P, _I, _P]),
     "gpmpc_plant_step": (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_rollout": (_I, [_P, _I, _I, _P, _P, _I, _P, _P]),
     "gpmpc_preprocess": (_I, [_P, _I, _P, _P, _P, _I, _P, _D, _D, _P, _P, _P]),
     "gpmpc_gp_informative": (_I, [_P, _I, _P, _P, _I, _P, _P, _P]),
     "gpmpc_gp_select": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),

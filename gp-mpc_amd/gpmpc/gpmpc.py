@@ -23,7 +23,7 @@ from . import _lib
 from .gp import LOVE_CHOLESKY_ROWS, GaussianProcess, fit_gp
 from .models import ModelSpec, get_spec
 from .mpc import MPC
-from .solver import BatchSolver, STATUS_NAMES, inverse_cdf, setup_prior_dynamics
+from .solver import BatchSolver, STATUS_NAMES, inverse_cdf, predict_trajectory, setup_prior_dynamics
 
 
 class GPMPC:
@@ -628,6 +628,15 @@ class GPMPC:
                 i = int(torch.nonzero(bad)[0])
                 raise AssertionError(f"instance {i}: unexpected status {int(self.solver.status[i])}")
         return u0
+
+    def predict_trajectory(self, x0, u, with_gp: bool = True, return_var: bool = False):
+        """What the controller believes will happen: the open-loop rollout of its model from ``x0`` under the
+        inputs ``u`` (``BatchSolver.rollout``), the learned GP means included unless ``with_gp=False`` (the prior
+        alone).  numpy in and out: one trajectory, ``x0`` (nx,) and ``u`` (T, nu), gives (T+1, nx); a batch,
+        (P, nx) and (P, T, nu), gives (P, T+1, nx).  ``return_var=True`` adds the GPs' posterior variances along
+        it, (T, n_gp) or (P, T, n_gp).  The GPs must be uploaded (``reset()`` after ``train_gp``)."""
+        assert not (with_gp and getattr(self, "_requires_recompile", False)), "GP model must be uploaded (call reset())"
+        return predict_trajectory(self.solver, x0, u, with_gp=with_gp, return_var=return_var)
 
     def reference_trajectory(self) -> np.ndarray:
         """`gpmpc/gpmpc.py:509-514`."""

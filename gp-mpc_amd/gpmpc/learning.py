@@ -202,11 +202,44 @@ def tracking_cost(data: dict, traj: np.ndarray, tstep0: np.ndarray | None = None
     return float(((obs - ref) ** 2).sum(-1).mean())
 
 
+def prediction_error(ctrl, data: dict, horizon: int, stride: int = 1, with_gp: bool = True) -> np.ndarray:
+    """Multi-step prediction error of the controller's model on a recorded run: the standard check of a learned
+    model, no counterpart in the reference.  ``data`` is a :func:`run_evaluation` dict, ``obs`` (S+1, B, nx) and
+    ``action`` (S, B, nu).  Every window starting at s = 0, stride, 2 stride, ... <= S - horizon is rolled out
+    open-loop from ``obs[s]`` under the recorded actions, all windows and instances in one
+    ``ctrl.solver.rollout`` call (P = windows x B).  Returns (horizon, nx): the root mean square over windows and
+    instances of ``x_pred[k] - obs[s + k]``, k = 1 .. horizon.  ``with_gp=False`` gives the prior's curve to set
+    beside the learned model's."""
+    obs = np.asarray(data["obs"], dtype=np.float64)
+    act = np.asarray(data["action"], dtype=np.float64)
+    S, B = act.shape[:2]
+    horizon, stride = int(horizon), int(stride)
+    if horizon < 1 or stride < 1:
+        raise ValueError("horizon and stride must be at least 1")
+    if horizon > S:
+        raise ValueError(f"horizon {horizon} exceeds the run's {S} steps")
+    starts = np.arange(0, S - horizon + 1, stride)
+    steps = starts[:, None] + np.arange(horizon + 1)[None, :]                       # (W, horizon+1)
+    x0 = obs[starts].reshape(len(starts) * B, -1)                                    # window-major, then instance
+    u = act[steps[:, :horizon]].transpose(0, 2, 1, 3).reshape(len(starts) * B, horizon, -1)
+    want = obs[steps].transpose(0, 2, 1, 3).reshape(len(starts) * B, horizon + 1, -1)
+    solver = ctrl.solver
+    x = solver.rollout(torch.as_tensor(np.ascontiguousarray(x0), device=solver.device),
+                       torch.as_tensor(np.ascontiguousarray(u), device=solver.device), with_gp=with_gp)
+    err = x.cpu().numpy()[:, 1:] - want[:, 1:]
+    return np.sqrt((err ** 2).mean(axis=0))
+
+
 def learn(n_epochs: int, ctrl, lr: float, gp_iterations: int, seed: int, samples_per_epoch: int,
-          episode_len: int, x0: np.ndarray | None = None, tstep0: np.ndarray | None = None):
+          episode_len: int, x0: np.ndarray | None = None, tstep0: np.ndarray | None = None,
+          report_prediction: int = 0):
     """Episodic learning (`scripts/run_gp_mpc.py:86-137`): epoch 0 runs the prior MPC; every
     epoch then fits the GPs on all data gathered so far and runs a test and a train episode
-    batch with GP-MPC.  Returns (train_runs, test_runs, timing) dicts keyed by epoch."""
+    batch with GP-MPC.  Returns (train_runs, test_runs, timing) dicts keyed by epoch.
+
+    ``report_prediction=h > 0``: every epoch's test run also records :func:`prediction_error` at horizon h on
+    itself, the learned model's curve and the prior's, under the key ``"prediction_error"`` of its dict:
+    ``{"gp": (h, nx), "prior": (h, nx)}``.  Off by default, which leaves the returned runs as they were."""
     from . import distributed as D
 
     spec = ctrl.model
@@ -237,6 +270,10 @@ def learn(n_epochs: int, ctrl, lr: float, gp_iterations: int, seed: int, samples
         t5 = time.perf_counter()
         train_runs[epoch] = run_evaluation(ctrl, x0, episode_len, tstep0)
         t6 = time.perf_counter()
+        if report_prediction > 0:
+            test_runs[epoch]["prediction_error"] = {
+                "gp": prediction_error(ctrl, test_runs[epoch], report_prediction),
+                "prior": prediction_error(ctrl, test_runs[epoch], report_prediction, with_gp=False)}
         timing[epoch] = {"train_gp": t4 - t3, "test": t5 - t4, "collect": t6 - t5, "n_train": len(x_train)}
     return train_runs, test_runs, timing
 

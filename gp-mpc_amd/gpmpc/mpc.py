@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .models import ModelSpec, get_spec
-from .solver import BatchSolver, STATUS_NAMES
+from .solver import BatchSolver, STATUS_NAMES, predict_trajectory
 
 
 class MPC:
@@ -84,6 +84,11 @@ class MPC:
             tstep = self._tstep
             self.traj_step += 1
         return s.solve(obs, tstep)
+
+    def predict_trajectory(self, x0, u, return_var: bool = False):
+        """The open-loop rollout of the prior model from ``x0`` under the inputs ``u`` (``BatchSolver.rollout``
+        with ``with_gp=False``): ``GPMPC.predict_trajectory`` without the GPs, same shapes."""
+        return predict_trajectory(self.solver, x0, u, with_gp=False, return_var=return_var)
 
     def reference_trajectory(self) -> np.ndarray:
         """`gpmpc/mpc.py:188-193`."""

@@ -52,6 +52,28 @@ def _c(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
+def predict_trajectory(solver, x0, u, with_gp: bool = True, return_var: bool = False):
+    """numpy front of ``solver.rollout`` (``GPMPC.predict_trajectory`` / ``MPC.predict_trajectory``): one trajectory,
+    ``x0`` (nx,) and ``u`` (T, nu), gives ``x`` (T+1, nx); a batch, (P, nx) and (P, T, nu), gives (P, T+1, nx).  With
+    ``return_var`` also the GP variances (T, n_gp) / (P, T, n_gp)."""
+    x0 = np.asarray(x0, dtype=np.float64)
+    u = np.asarray(u, dtype=np.float64)
+    single = x0.ndim == 1
+    if single:
+        if u.ndim != 2:
+            raise ValueError("one trajectory takes x0 (nx,) and u (T, nu)")
+        x0, u = x0[None], u[None]
+    elif x0.ndim != 2 or u.ndim != 3 or u.shape[0] != x0.shape[0]:
+        raise ValueError("a batch takes x0 (P, nx) and u (P, T, nu)")
+    dev = solver.device
+    out = solver.rollout(torch.as_tensor(np.ascontiguousarray(x0), device=dev),
+                         torch.as_tensor(np.ascontiguousarray(u), device=dev), with_gp=with_gp, var=return_var)
+    out = tuple(t.cpu().numpy() for t in (out if return_var else (out,)))
+    if single:
+        out = tuple(a[0] for a in out)
+    return out if return_var else out[0]
+
+
 class BatchSolver:
     """One solver handle for ``batch`` instances of ``spec`` with horizon ``horizon``.
 
@@ -697,3 +719,27 @@ class BatchSolver:
                                              out.data_ptr(), None if tstep is None else tstep.data_ptr(),
                                              self._stream()))
         return out
+
+    def rollout(self, x0: torch.Tensor, u: torch.Tensor, with_gp: bool = True, var: bool = False):
+        """Open-loop rollout of the model the MPC plans with (gpmpc_rollout): ``x0`` (P, nx) and ``u`` (P, T, nu)
+        on the solver's device give ``x`` (P, T+1, nx), row 0 a copy of ``x0`` and row k+1 one RK4 step from
+        ``(x_k, u_k)``: the discrete map of the SQP's shooting constraint, the GP means evaluated at every RK4
+        substage as the solver reads them (a FITC mean included).  ``with_gp=False`` rolls the prior alone (the
+        nominal MPC's model; no GP needs to be set).  With ``var=True`` also (P, T, n_gp): each GP's exact
+        posterior variance without likelihood noise at ``z_k[gp_src_g]``, as ``gp_predict`` returns it.  P is
+        independent of the solver's batch, and a trajectory's result does not depend on the others.  The inputs
+        must be complete when the library reads them, so the call synchronises the current stream first; it
+        returns with its work completed (it runs on a stream of the handle's own)."""
+        x0 = x0.to(self.device, torch.float64).contiguous()
+        u = u.to(self.device, torch.float64).contiguous()
+        if x0.ndim != 2 or x0.shape[1] != self.nx:
+            raise ValueError(f"x0 must be (P, nx={self.nx})")
+        if u.ndim != 3 or u.shape[0] != x0.shape[0] or u.shape[2] != self.nu:
+            raise ValueError(f"u must be (P={x0.shape[0]}, T, nu={self.nu})")
+        P, T = int(u.shape[0]), int(u.shape[1])
+        x = torch.empty(P, T + 1, self.nx, dtype=torch.float64, device=self.device)
+        v = torch.empty(P, T, self.spec.n_gp, dtype=torch.float64, device=self.device) if var else None
+        torch.cuda.current_stream(self.device).synchronize()
+        _lib.check(self.lib.gpmpc_rollout(self._h, P, T, x0.data_ptr(), u.data_ptr(), int(bool(with_gp)), x.data_ptr(),
+                                          _lib.ptr(v)))
+        return (x, v) if var else x

@@ -24,6 +24,10 @@
  * gpmpc_gp_inducing takes no stream: it is a synchronous builder in the class of gpmpc_gp_reserve, with no
  * device input of the caller's, and it keeps the rule on a stream the handle owns, which waits for the
  * handle's event first and carries the record when the call returns, its work completed.
+ * gpmpc_rollout takes no stream either and keeps the rule the same way: its launches run on that stream of the
+ * handle's, behind the handle's last call whatever stream that was on, and the stream is drained before the call
+ * returns.  Unlike gpmpc_gp_inducing it has device inputs of the caller's, and they are the caller's to order:
+ * x0_dev and u_dev must be complete when the call is made; the outputs are complete when it returns.
  * The library reads no environment variables: every option is an explicit call.
  */
 #ifndef GPMPC_MI355X_H
@@ -428,6 +432,34 @@ gpmpc_status gpmpc_gp_posterior(int32_t n, int32_t d, int32_t npad, const double
  * host synchronisation, whether the parameters change or not. */
 gpmpc_status gpmpc_plant_step(gpmpc_handle* h, int32_t batch, const double* params, const double* x,
                               const double* u, double* x_next, int32_t* tstep, void* stream);
+
+/* Open-loop rollout of the model the MPC plans with: P trajectories of T steps, one launch
+ * (csrc/sqp_kernel.hip rollout_kernel).  x0_dev [P][nx] and u_dev [P][T][nu] are device inputs; x_dev
+ * [P][T+1][nx] is the device output: row 0 a copy of x0, row k+1 one RK4 step of length dt from (x_k, u_k)
+ * (the RK4 of the build, gpmpc/gpmpc.py:204-209, over the residual dynamics of gpmpc/gpmpc.py:171-199).
+ *   with_gp = 1  the prior at gpmpc_set_model's parameters plus the GP means as the solver reads them (the
+ *                handle's tile packs: a FITC mean installed by gpmpc_gp_fitc or uploaded by gpmpc_set_gp is the
+ *                one used), evaluated at z[gp_src_g] at each of the four RK4 substages: the discrete map of the
+ *                SQP's multiple-shooting constraint.
+ *   with_gp = 0  the GP means are zero: the nominal MPC's model.  Nothing of the GPs is read, none needs to be set.
+ * With with_gp = 0 the states are the bits of T chained gpmpc_plant_step calls at the same parameters.
+ * var_dev [P][T][n_gp], may be NULL: the exact posterior variance without likelihood noise of GP g at
+ * z_k[gp_src_g], z_k = [x_k; u_k], k = 0 .. T-1, by the launch behind gpmpc_gp_predict(with_noise = 0) on the
+ * finished trajectory and bit-identical to that call on those inputs (a LOVE root is ignored, a FITC overlay does
+ * not change it).  Allowed with with_gp = 0: the uncertainty along a prior rollout.
+ * What is computed for a trajectory depends on its own inputs and the handle only: the same (x0, u) gives the same
+ * bits whatever P is and wherever it sits in the batch, and the first k+1 rows of a T-step rollout are the bits of
+ * a k-step rollout.  A non-finite state or input makes that trajectory's later rows non-finite and touches no other
+ * trajectory; nothing is refused on the device.
+ * THE CALL IS SYNCHRONOUS and takes no stream (see "Streams" above).  The gathered variance inputs (P T points) are
+ * scratch of the handle, allocated inside the call and kept for a later call of the same or a smaller size; if the
+ * allocation fails the call returns GPMPC_ERR_NOMEM and the handle is unchanged.
+ * Refused with nothing written: P < 1, T < 1, x0_dev, u_dev or x_dev NULL, with_gp not 0 or 1, P (T+1) nx not
+ * representable in int32 (GPMPC_ERR_ARG); a call before gpmpc_set_model, with_gp = 1 while the handle's GPs are
+ * off (gpmpc_use_gp(0), or a GP of the model not set), var_dev with a GP not set or set without Linv
+ * (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_rollout(gpmpc_handle* h, int32_t P, int32_t T, const double* x0_dev, const double* u_dev,
+                           int32_t with_gp, double* x_dev, double* var_dev);
 
 /* GP training rows from transitions, on the device: GPMPC.preprocess_data of the build (the reference's
  * gpmpc/gpmpc.py:113-151) for the handle's model, csrc/gp_observe.hip.  x_dev [P][nx], u_dev [P][nu] and
