@@ -3681,6 +3681,12 @@ struct SqpKernel {
 #pragma unroll
             for (int i = 0; i < NX; ++i) xn[i] = dpp_d<0x130>(w[i]);   // wave_shl:1, stage k + 1 (lane 63 unused)
             double r_stat = 0.0, r_eq = 0.0, r_ineq = 0.0, r_comp = 0.0;
+            // fmax returns its other operand when one is NaN, so the four norms drop a NaN term (and with it
+            // the Inf - Inf of a non-finite iterate, multiplier or tightened bound) instead of carrying it:
+            // each term's finiteness is gathered beside its fmax, one flag per lane and one ballot.  (The
+            // complementarity products need no test of their own: their factors are a multiplier, finite
+            // when the stationarity term is, and a bound distance, tested as it stands.)
+            bool rfin = true;
             double g[NB];
 #pragma unroll
             for (int v = 0; v < NB; ++v) {
@@ -3688,9 +3694,13 @@ struct SqpKernel {
                 g[v] = av ? hdiag(P, v, lane, H) * (w[v] - yr[v]) : 0.0;
                 if (av) {
                     const double lb = lbv(v), ub = ubv(v);
-                    r_stat = fmax(r_stat, fabs(g[v] - lamL[v] + lamU[v] + ct[v]));
-                    r_ineq = fmax(r_ineq, fmax(lb - w[v], w[v] - ub));
-                    r_comp = fmax(r_comp, fmax(fabs(lamL[v] * (w[v] - lb)), fabs(lamU[v] * (ub - w[v]))));
+                    const double ts = g[v] - lamL[v] + lamU[v] + ct[v];
+                    const double tl = lb - w[v], tu = w[v] - ub;
+                    const double cl = lamL[v] * (w[v] - lb), cu = lamU[v] * (ub - w[v]);
+                    r_stat = fmax(r_stat, fabs(ts));
+                    r_ineq = fmax(r_ineq, fmax(tl, tu));
+                    r_comp = fmax(r_comp, fmax(fabs(cl), fabs(cu)));
+                    rfin = rfin && __builtin_isfinite(ts) && __builtin_isfinite(tl) && __builtin_isfinite(tu);
                 }
             }
             double cq[NX];
@@ -3698,6 +3708,7 @@ struct SqpKernel {
             for (int i = 0; i < NX; ++i) {
                 cq[i] = act_u ? F[i] - xn[i] : 0.0;
                 r_eq = fmax(r_eq, fabs(cq[i]));
+                rfin = rfin && __builtin_isfinite(cq[i]);
             }
             if (lane == 0) {
 #pragma unroll
@@ -3705,12 +3716,14 @@ struct SqpKernel {
                     r_ineq = fmax(r_ineq, fabs(x0[i] - w[i]));  // lbx = ubx = obs
                     // stage-0 state rows on the iterate's x_0 (= obs after the first step)
                     r_ineq = fmax(r_ineq, fmax(P.x_lo[i] - P.uh - w[i], w[i] - P.x_hi[i] - P.uh));
+                    rfin = rfin && __builtin_isfinite(w[i]);   // (x0 and the box are finite: x0_ok)
                 }
             }
             res[0] = wave_max(r_stat);
             res[1] = wave_max(r_eq);
             res[2] = wave_max(r_ineq);
             res[3] = wave_max(r_comp);
+            if (__builtin_amdgcn_ballot_w64(!rfin) != 0) { status = kNaN; break; }
             if (!(res[0] == res[0] && res[1] == res[1] && res[2] == res[2] && res[3] == res[3])) { status = kNaN; break; }
             if (res[0] <= P.tol_stat && res[1] <= P.tol_eq && res[2] <= P.tol_ineq && res[3] <= P.tol_comp) {
                 status = kSuccess;
@@ -3816,7 +3829,7 @@ struct SqpKernel {
 #pragma unroll
                 for (int i = 0; i < NX; ++i) w[i] = x0[i];
             }
-            if (wave_min(fin ? 1.0 : 0.0) < 0.5) { status = kNaN; break; }
+            if (__builtin_amdgcn_ballot_w64(!fin) != 0) { status = kNaN; break; }   // (a ballot, not an f64 wave_min of 0 / 1)
         }
         TPHASE(7);
 #ifdef GPMPC_TIMING

@@ -57,7 +57,15 @@ enum { GPMPC_MODEL_QUAD2D = 0, GPMPC_MODEL_QUAD3D = 1, GPMPC_MODEL_CARTPOLE = 2 
  * (gpmpc/gpmpc.py:288,296,309-310; gpmpc/mpc.py:141,145,157-158) by more than the inequality
  * tolerance makes the QP infeasible: GPMPC_QP_FAILURE, as acados reports it.  After a failed
  * solve (NAN or QP_FAILURE) the instance keeps its previous iterate, its multipliers restart
- * from zero and its next solve runs untightened (no poisoning of later steps). */
+ * from zero and its next solve runs untightened (no poisoning of later steps).
+ * GPMPC_NAN: a non-finite value (NaN or Inf) in anything the NLP residuals read -- the stored
+ * iterate, the dynamics at it, the multipliers, the tightened bounds -- at the iteration that
+ * meets it, or a non-finite iterate after a full step.  A non-finite STORED iterate (a
+ * gpmpc_set_iterate from a gpmpc_rollout that returned NaN, say) therefore ends the solve at
+ * iteration 0 with GPMPC_NAN whatever the other terms are.  The iterate is kept like any failed
+ * solve's, which here means it stays non-finite -- and every later solve of the instance ends the
+ * same way -- until gpmpc_set_iterate or gpmpc_reset(reset_iterate = 1) replaces it, and u0 is
+ * the kept iterate's first input (NaN when that is where the NaN sits). */
 enum { GPMPC_SUCCESS = 0, GPMPC_NAN = 1, GPMPC_MAXITER = 2, GPMPC_MINSTEP = 3, GPMPC_QP_FAILURE = 4 };
 
 /* Create a solver for `max_batch` independent instances of model `model_id` with horizon

@@ -624,17 +624,23 @@ struct Instance {
             for (int i = 0; i < n; ++i) g[i] = hd[i] * (w[i] - yref[i]);
             ctmul(pi.data(), ctp.data());
             double rs = 0, re = 0, ri = 0, rc = 0;
+            // std::max(a, b) keeps a when b is NaN, so the norms drop a NaN term instead of carrying it:
+            // every term's finiteness is gathered beside them (a non-finite iterate, F, C'pi, multiplier
+            // or bound ends the solve as kNaN at this iteration)
+            bool rfin = true;
+            auto term = [&rfin](double v) { rfin = rfin && std::isfinite(v); return v; };
             for (int i = 0; i < n; ++i) {
-                rs = std::max(rs, std::fabs(g[i] + ctp[i] - ll[i] + lu[i]));
-                ri = std::max(ri, std::max(std::max(lbw[i] - w[i], w[i] - ubw[i]), 0.0));
-                rc = std::max(rc, std::max(std::fabs(ll[i] * (w[i] - lbw[i])), std::fabs(lu[i] * (ubw[i] - w[i]))));
+                rs = std::max(rs, std::fabs(term(g[i] + ctp[i] - ll[i] + lu[i])));
+                ri = std::max(ri, std::max(std::max(term(lbw[i] - w[i]), term(w[i] - ubw[i])), 0.0));
+                rc = std::max(rc, std::max(std::fabs(term(ll[i] * (w[i] - lbw[i]))), std::fabs(term(lu[i] * (ubw[i] - w[i])))));
             }
             for (int k = 0; k < H; ++k)
-                for (int i = 0; i < nx; ++i) re = std::max(re, std::fabs(F[k * nx + i] - xs[(k + 1) * nx + i]));
+                for (int i = 0; i < nx; ++i) re = std::max(re, std::fabs(term(F[k * nx + i] - xs[(k + 1) * nx + i])));
             for (int i = 0; i < nx; ++i) {
-                ri = std::max(ri, std::fabs(x0[i] - xs[i]));
+                ri = std::max(ri, std::fabs(term(x0[i] - xs[i])));
                 ri = std::max(ri, std::max(P.xlo[i] - P.uh - xs[i], xs[i] - P.xhi[i] - P.uh));
             }
+            if (!rfin) rs = NAN;
             if (trace) std::fprintf(stderr, "  sqp %d: stat %.3e eq %.3e ineq %.3e comp %.3e (qp iters so far %d)\n", it, rs, re, ri, rc, qp_total);
             if (!(rs == rs && re == re && ri == ri && rc == rc)) { status = kNaN; break; }
             if (rs <= P.tol && re <= P.tol && ri <= P.tol && rc <= P.tol) { status = kSuccess; break; }
