@@ -30,6 +30,16 @@ parts of whole column tiles, a balanced tree), `redundant_ld` is the same recurs
 precision of the GP's data.  Over RED_CASES and GPU_RED_CASES the smallest gap between the best score and the
 runner-up is 4.5e-9 (n = 272) against a float64 score error of 9e-16 there (2.4e-14 at worst, n = 40 with 33 rows
 gone): factors of 5e6 and more.  The one step without a gap is the last of m = n - 1 (`structural_tie`).
+
+Three GPs (`model_red_case`): quad3d's GPs of 40 rows each, drawn over the range of the model's transitions, each
+with its own lengthscale (M_RED_ELL), outputscale and noise (M_RED_HYP), m = 33; and the same with row 39 inert in GP 1
+only (a rejected append there, an accepted one in GPs 0 and 2), which `redundant_ld` takes as a `live` mask.  Measured
+with tests/test_gp_redundant_cpu.py -s: the smallest gap is 1.09e-7 against a worst float64 score error of 8.0e-13, the
+smallest factor 1.4e5 (step 29); with the inert row 3.5e-8 against 7.9e-13, the smallest factor 4.5e4 (step 32): the
+same condition, GAP_FACTOR, as the quad2d cases, and the GPU test holds the device's scores to gap / GAP_FACTOR of
+the model as theirs does.  Every GP decides a pick (`red_decided_by`): GP 1 from step 0, GP 2 at step 4 (1 with the inert
+row), GP 0 at step 8; leaving one out or scoring it with GP 0's outputscale and noise changes the picks.  The inert row
+is not forced out first: it is picked at step 1 with the score 2.2e-3 of the GPs in which it is live.
 """
 
 from __future__ import annotations
@@ -246,12 +256,14 @@ def precision_ld(X, ell, sf2=SF2, sn2=SN2):
     return Li.T @ Li
 
 
-def redundant_ld(Ps, hyp, m, forced=None):
-    """The same recursion in longdouble on the precisions Ps (n, n) (every row live).  Per step: the pick, its score,
-    the gap to the runner-up and the scores of all open rows (for the model's error)."""
+def redundant_ld(Ps, hyp, m, forced=None, live=None):
+    """The same recursion in longdouble on the precisions Ps (n, n).  `live` (per GP a mask of n rows, default: every
+    row) marks the rows that are not inert in that GP; an inert row's row and column of Ps[g] are zero, its term is 0
+    and it conditions nothing in g.  Per step: the pick, its score, the gap to the runner-up and the scores of all
+    open rows (for the model's error)."""
     n = Ps[0].shape[0]
     p = [np.diag(P).copy() for P in Ps]
-    live = [np.ones(n, dtype=bool) for _ in Ps]
+    live = [np.ones(n, dtype=bool) for _ in Ps] if live is None else [np.asarray(l, dtype=bool) for l in live]
     cols = [np.zeros((m, n), dtype=LD) for _ in Ps]
     open_ = np.ones(n, dtype=bool)
     picks, scores, gaps, tables = [], [], [], []
@@ -266,6 +278,8 @@ def redundant_ld(Ps, hyp, m, forced=None):
         scores.append(s[j])
         tables.append(np.where(open_, s, LD(np.nan)))
         for g, P in enumerate(Ps):
+            if not live[g][j]:
+                continue
             c = (P[:, j] - cols[g][:t].T @ cols[g][:t, j]) / np.sqrt(p[g][j])
             cols[g][t] = c
             p[g] = p[g] - c * c
@@ -292,3 +306,82 @@ def score_error(model_table, ref_table):
     """The worst |model - reference| over the open rows of one step's scores."""
     keep = ~np.isnan(ref_table.astype(np.float64))
     return float(np.abs(model_table[keep] - ref_table[keep].astype(np.float64)).max())
+
+
+# --------------------------------------------------------------- three GPs with their own outputscale and noise each
+# quad3d: n = M_RED_N rows per GP (the call ranks the same rows in all), inputs over the range of the model's
+# transitions (gp_select_ref.input_box), (sf2, sn2) and the lengthscale distinct per GP
+M_RED_N, M_RED_M = 40, 33
+M_RED_HYP = ((2.5, 1e-3), (0.7, 4e-3), (1.3, 2e-3))
+M_RED_ELL = (0.015, 0.25, 0.3)
+M_RED_SEED = 520
+M_INERT = (1, 39)   # (GP, row): the row that is inert in that GP only
+_MRED: dict = {}
+
+
+def model_red_data(name="quad3d", n=M_RED_N):
+    import gp_select_ref as S
+
+    out = []
+    for g, (lo, hi) in enumerate(S.input_box(name)):
+        rng = np.random.default_rng(M_RED_SEED + 31 * g)
+        X = rng.uniform(lo, hi, (n, len(lo)))
+        out.append(dict(X=X, y=D.targets(X), ell=M_RED_ELL[g], d=len(lo), Z=rng.uniform(lo, hi, (D.NPTS, len(lo)))))
+    return out
+
+
+def model_red_case(m=M_RED_M, inert=False):
+    """quad3d's three GPs of M_RED_N rows, their upload states, the model's and the reference's run.  `inert`: row
+    M_INERT[1] is inert in GP M_INERT[0] (a rejected append of one row after an upload of the rows before it) and was
+    appended to the other GPs (gp_drop_ref.append_block)."""
+    if (m, inert) not in _MRED:
+        dat, hyp, n = model_red_data(), list(M_RED_HYP), M_RED_N
+        gi, row = M_INERT
+        assert row == n - 1
+        states, Ps, live = [], [], []
+        for g, (dg, (sf2, sn2)) in enumerate(zip(dat, hyp)):
+            lv = np.ones(n, dtype=bool)
+            if not inert:
+                states.append(D.upload_state(dg["X"], dg["y"], dg["ell"], sf2, sn2))
+                Ps.append(precision_ld(dg["X"], dg["ell"], sf2, sn2))
+            else:
+                st = D.upload_state(dg["X"][:row], dg["y"][:row], dg["ell"], sf2, sn2)
+                if g == gi:
+                    states.append(D.with_inert(st, row, 1))
+                    P = np.zeros((n, n), dtype=LD)
+                    P[:row, :row] = precision_ld(dg["X"][:row], dg["ell"], sf2, sn2)
+                    Ps.append(P)
+                    lv[row] = False
+                else:
+                    states.append(D.append_block(st, dg["X"][row:], dg["y"][row:], dg["ell"], sf2, sn2))
+                    Ps.append(precision_ld(dg["X"], dg["ell"], sf2, sn2))
+            live.append(lv)
+        model = redundant_f64([s[1] for s in states], hyp, m)
+        ref = redundant_ld(Ps, hyp, m, live=live)
+        _MRED[(m, inert)] = dict(data=dat, hyp=hyp, states=states, model=model, ref=ref, Ps=Ps, live=live)
+    return _MRED[(m, inert)]
+
+
+def red_decided_by(Ps, hyp, live, picks, err=0.0):
+    """Per GP the steps at which it decides the pick: its term of the picked row is the largest over the GPs (the
+    row's score is that GP's) and stays so when moved by err either way.  Recomputed from the picks."""
+    n = Ps[0].shape[0]
+    p = [np.diag(P).copy() for P in Ps]
+    cols = [[] for _ in Ps]
+    out = [[] for _ in Ps]
+    for t, j in enumerate(int(v) for v in picks):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            terms = np.array([float((1 / p[g][j] - LD(hyp[g][1])) / LD(hyp[g][0])) if live[g][j] else 0.0 for g in range(len(Ps))])
+        g = int(terms.argmax())
+        if terms[g] - err > np.delete(terms, g).max() + err:
+            out[g].append(t)
+        for q, P in enumerate(Ps):
+            if not live[q][j]:
+                continue
+            c = P[:, j].copy()
+            for cc in cols[q]:
+                c -= cc * cc[j]
+            c = c / np.sqrt(p[q][j])
+            cols[q].append(c)
+            p[q] = p[q] - c * c
+    return out

@@ -37,6 +37,25 @@ Clustered pool (CLUSTERS = 8 transitions, each repeated COPIES = 16 times with p
 that tracks one reference produces; GPs of 40 rows).  After m = 16 picks the largest residual score left in the pool
 is 1.39e-4 with the greedy rule, whose picks come from six of the eight transitions, against 3.07e-4 with the top-16
 rank rule (observe_ref.rank), whose picks are all copies of one: a ratio of 0.45.
+
+Other models (M_CASES; model_data, model_points, model_base, model_ref).  quad3d: three GPs of 24, 272 and 40 rows
+(input dimensions 1, 3, 3); cartpole: two GPs of 24 and 40 rows that read the same three columns of z.  Every GP has
+its own lengthscale (M_ELL), outputscale (M_SF2), noise (M_SN2) and training rows, drawn uniformly over the box the
+GP's inputs span over BOX_POINTS transitions (input_box), so the start scores spread (6e-4 .. 4e-2 over a pool of 40).
+Pools of 40 and 130 candidates (quad3d) and 40 (cartpole) with m = 1, 17, 33, and one quad3d pool of a single
+candidate.  Besides the duplicate, candidate NANROW holds a NaN in a state column a GP reads (quad3d: x[:, 10], GP 2
+alone) and candidate NANROW2 one in a state column no GP reads, which must change nothing.  Measured with
+tests/test_gp_select_cpu.py -s:
+  * e_model / e_full of `greedy_f64` is at most 1.074 over the pools of 40 and 130 (quad3d, P = 40, m = 1, gp2; 0.25 ..
+    1.07 over all of them), within R_MODEL: their GPU tests use MARGIN_SELECT.  The single candidate gives 24.24
+    (quad3d, P = 1, m = 1, gp1: e_model 2.2e-16 against e_full 9.1e-18, a yardstick that happens to round well, as
+    in the quad2d case that set R_MODEL): that case alone has R_MODEL_ONE = 24.24, MARGIN_SELECT_ONE = ceil(4 x 24.24)
+    = 97 (`margin_for`).
+  * The smallest gap is 1.01e-6 (cartpole, P = 40, m = 33, step 22) against an allowed score error of 2.4e-14, a factor
+    4.2e7, which is also the smallest factor (quad3d: 1.9e8 at P = 40, m = 33, step 25).
+  * Every GP decides a pick (`decided_by`: its term is the largest at the picked candidate by more than the allowed
+    error both ways): quad3d P = 40 at steps 0 (GP 0), 1 (GP 1), 2 (GP 2), P = 130 at steps 2, 1, 0; cartpole at steps
+    0 and 4.  Leaving a GP out, or giving it GP 0's outputscale and noise in the loop, changes the picks at those steps.
 """
 
 from __future__ import annotations
@@ -273,3 +292,104 @@ def clustered_pool(spec, seed=9):
     x = np.repeat(x, COPIES, axis=0) + 1e-3 * rng.standard_normal((CLUSTERS * COPIES, x.shape[1]))
     u = np.repeat(u, COPIES, axis=0) + 1e-3 * rng.standard_normal((CLUSTERS * COPIES, u.shape[1]))
     return x, u
+
+
+# ------------------------------------------------------------------------- the other models: three GPs, shared inputs
+# quad3d: three GPs (input dimensions 1, 3, 3 of a gathered row of 7 columns) of 24, 272 and 40 rows; cartpole: two GPs
+# that read the same three columns, of 24 and 40 rows.  Nothing but cartpole's input columns is shared between GPs.
+M_SF2 = (2.5, 0.7, 1.3)
+M_SN2 = (1e-3, 4e-3, 2e-3)
+M_ROWS = {"quad3d": (24, 272, 40), "cartpole": (24, 40)}
+M_ELL = {"quad3d": (0.06, 0.15, 0.22), "cartpole": (2.6, 4.1)}
+M_SEED = {"quad3d": 300, "cartpole": 400}
+M_PS = {"quad3d": (40, 130), "cartpole": (40,)}
+# the candidate with a NaN in a state column that a GP reads (quad3d: x[:, 10], read by GP 2 alone) and the one with a
+# NaN in a state column no GP reads
+NANROW2, READ_COL, UNREAD_COL = 11, {"quad3d": 10, "cartpole": 3}, 0
+BOX_POINTS, BOX_SEED = 512, 77
+
+M_CASES = [(name, P, m) for name in M_ROWS for P in M_PS[name] for m in ms_for(P)] + [("quad3d", 1, 1)]
+# the model's ratio in the one case with a single candidate (quad3d, P = 1, m = 1, gp1), and its margin
+R_MODEL_ONE = 24.24
+MARGIN_SELECT_ONE = float(math.ceil(4 * R_MODEL_ONE))
+
+
+def margin_for(P):
+    """The margin of the model cases with P candidates."""
+    return MARGIN_SELECT_ONE if P == 1 else MARGIN_SELECT
+
+
+def model_points(spec, P, seed=5, unread_nan=True):
+    """P transitions' (x, u) with the duplicate, the NaN a GP reads and the NaN none reads (where P has room)."""
+    x, u = OR.transitions(spec, P, seed=seed)
+    if P > NANROW2:
+        x[DUP[1]], u[DUP[1]] = x[DUP[0]], u[DUP[0]]
+        x[NANROW, READ_COL[spec.name]] = np.nan
+        if unread_nan:
+            x[NANROW2, UNREAD_COL] = np.nan
+    return x, u
+
+
+@lru_cache(maxsize=None)
+def input_box(name):
+    """Per GP (lo, hi) of its inputs over BOX_POINTS transitions of the model: where the candidates lie."""
+    from gpmpc.models import get_spec
+
+    spec = get_spec(name)
+    return [(Z.min(0), Z.max(0)) for Z in gp_inputs(spec, *OR.transitions(spec, BOX_POINTS, seed=BOX_SEED))]
+
+
+@lru_cache(maxsize=None)
+def model_data(name, rows=None):
+    """Per GP of the model dict(X, y, ell, sf2, sn2, Z, d): rows[g] training inputs uniform over input_box, each GP from
+    its own seed (cartpole's two GPs read the same columns of z and hold different rows)."""
+    rows = M_ROWS[name] if rows is None else rows
+    out = []
+    for g, ((lo, hi), n) in enumerate(zip(input_box(name), rows)):
+        rng = np.random.default_rng(M_SEED[name] + 31 * g)
+        X = rng.uniform(lo, hi, (max(n, M_ROWS[name][g]), len(lo)))[:n]
+        out.append(dict(X=X, y=D.targets(X), ell=M_ELL[name][g], sf2=M_SF2[g], sn2=M_SN2[g], d=len(lo),
+                        Z=rng.uniform(lo, hi, (D.NPTS, len(lo)))))
+    return out
+
+
+@lru_cache(maxsize=None)
+def model_base(name, P):
+    """(gps, Zs, prep, finite) of the model's cases with P candidates."""
+    from gpmpc.models import get_spec
+
+    spec = get_spec(name)
+    gps = model_data(name)
+    Zs = gp_inputs(spec, *model_points(spec, P))
+    prep, finite = prepare_ld(gps, Zs)
+    return gps, Zs, prep, finite
+
+
+@lru_cache(maxsize=None)
+def model_ref(name, P, m):
+    gps, Zs, prep, finite = model_base(name, P)
+    return greedy_from(prep, finite, Zs, m)
+
+
+def decided_by(prep, ref, err):
+    """Per GP the steps of the run at which it decides the pick: its term d_g,j / sf2_g of the picked candidate j is
+    the largest over the GPs, and stays so when moved by err (the score error the criterion allows) either way.  The
+    terms are recomputed step by step from the run's picks."""
+    ds = [p["d"].copy() for p in prep]
+    ls = [[] for _ in prep]
+    out = [[] for _ in prep]
+    for t, j in enumerate(int(v) for v in ref["picks"]):
+        if not ref["finite"][j]:
+            continue
+        terms = np.array([float(d[j] / p["sf2"]) for d, p in zip(ds, prep)])
+        g = int(terms.argmax())
+        if terms[g] - err > np.delete(terms, g).max() + err:
+            out[g].append(t)
+        for q, p in enumerate(prep):
+            c = p["C"][:, j].copy()
+            for l in ls[q]:
+                c -= l * l[j]
+            l = c / np.sqrt(ds[q][j] + p["sn2"])
+            ls[q].append(l)
+            ds[q] = ds[q] - l * l
+    return out

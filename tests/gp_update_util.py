@@ -1,7 +1,8 @@
 """What the GPU tests of the device-side GP updates share (test_gpu_gp_append.py, test_gpu_gp_drop.py,
-test_gpu_gp_refactor.py): a quad2d BatchSolver per test file and name, uploads of the case's data
-(dicts with X, y, ell, Z, d per GP; sf2 = 1, sn2 = 1e-3), outputs pre-filled with NaN and followed
-by 64 sentinels, the unchanged-after-a-refusal check and the closed-loop comparison of two handles."""
+test_gpu_gp_refactor.py): a BatchSolver (quad2d unless the test names a model) per test file and name,
+uploads of the case's data (dicts with X, y, ell, Z, d per GP; sf2 = 1, sn2 = 1e-3), outputs pre-filled with
+NaN and followed by 64 sentinels, the unchanged-after-a-refusal check and the closed-loop comparison of two
+handles."""
 
 from contextlib import contextmanager
 
@@ -26,15 +27,15 @@ def gpu_torch():
     return torch
 
 
-def solver(owner, key, H=5, B=2, **kw):
-    """The BatchSolver `key` ("A", "B") of the test file `owner`: no two files share a handle."""
+def solver(owner, key, H=5, B=2, model="quad2d", **kw):
+    """The BatchSolver `key` ("A", "B") of the test file `owner` for `model`: no two files share a handle."""
     gpu_torch()
     from gpmpc.models import get_spec
     from gpmpc.solver import BatchSolver
 
-    if (owner, key) not in _SOLVERS:
-        _SOLVERS[(owner, key)] = BatchSolver(get_spec("quad2d"), H, B, **kw)
-    return _SOLVERS[(owner, key)]
+    if (owner, key, model) not in _SOLVERS:
+        _SOLVERS[(owner, key, model)] = BatchSolver(get_spec(model), H, B, **kw)
+    return _SOLVERS[(owner, key, model)]
 
 
 def hyp(dg):
@@ -55,10 +56,15 @@ def gp_objects(data, rows, hyps=None):
 
 
 def upload(s, data, rows, capacity=None, hyps=None):
+    """set_gps of the case's data (one dict per GP of the handle's model) on `rows`; `capacity`: one for every GP, or
+    one per GP (None: that GP keeps the uploaded size)."""
+    assert len(data) == s.spec.n_gp
     s.set_gps(gp_objects(data, rows, hyps))
     if capacity is not None:
-        for g in range(2):
-            s.reserve_gp(g, capacity)
+        caps = capacity if isinstance(capacity, (tuple, list)) else [capacity] * s.spec.n_gp
+        for g in range(s.spec.n_gp):
+            if caps[g] is not None:
+                s.reserve_gp(g, caps[g])
 
 
 def guarded(P, dtype=None):

@@ -1,7 +1,8 @@
 """The rows the GPs would miss least (gpmpc_gp_redundant), the parts that need no GPU: the float64 model in the
 kernel's summation order against the longdouble reference (the same picks, with the gap condition at every step),
 non-decreasing scores, the final p against the leave-one-out variances of the reduced GPs, and what the rule is worth
-on a window with clustered newest rows."""
+on a window with clustered newest rows; for quad3d's three GPs with their own hyperparameters (and a row inert in one
+of them only) also the scores against leave-one-out variances computed afresh, and that every GP decides a pick."""
 
 import numpy as np
 import pytest
@@ -74,6 +75,81 @@ def test_an_inert_row_scores_zero_and_is_picked_first():
     states[1] = D.upload_state(np.insert(dat[1]["X"], 9, 0.3, axis=0), np.insert(dat[1]["y"], 9, 0.1), dat[1]["ell"])
     out = DR.redundant_f64([s[1] for s in states], [(DR.SF2, DR.SN2)] * 2, 1)
     assert out["ok"] == 1 and out["scores"][0] > 0
+
+
+# ------------------------------------------------------- quad3d: three GPs, each with its own outputscale and noise
+@pytest.mark.parametrize("inert", [False, True], ids=["every row live", "a row inert in one GP"])
+def test_three_gp_model_picks_the_reference_rows_and_every_step_meets_the_gap_condition(inert):
+    c = DR.model_red_case(inert=inert)
+    model, ref, m = c["model"], c["ref"], DR.M_RED_M
+    assert model["ok"] == 1 and len({h for h in c["hyp"]}) == 3 and len({dg["ell"] for dg in c["data"]}) == 3
+    errs = np.array([DR.score_error(model["tables"][t], ref["tables"][t]) for t in range(m)])
+    factor = ref["gaps"] / errs
+    print(f"[redundant quad3d] inert {inert}: least gap {ref['gaps'].min():.3e}, worst score error {errs.max():.3e}, "
+          f"least factor {factor.min():.3e} (step {int(factor.argmin())}), picks {ref['picks'].tolist()}")
+    assert (ref["gaps"] >= DR.GAP_FACTOR * errs).all(), (ref["gaps"], errs)
+    assert model["picks"].tolist() == ref["picks"].tolist() and len(set(ref["picks"].tolist())) == m
+    s = np.asarray(ref["scores"], dtype=np.float64)
+    assert (np.diff(s) >= 0).all() and (s > 0).all()
+    if inert:
+        # the row is live in GPs 0 and 2: its score is theirs, it is not forced out first with score 0
+        g, row = DR.M_INERT
+        at = ref["picks"].tolist().index(row)
+        assert at > 0 and s[at] > 0 and not c["live"][g][row] and c["states"][g][1][row, row] == 0.0
+        rest = [q for q in range(3) if q != g]
+        alone = DR.redundant_ld([c["Ps"][q] for q in rest], [c["hyp"][q] for q in rest], 1, forced=[row])
+        assert float(ref["tables"][0][row]) == float(alone["scores"][0])
+
+
+def _loo_scores(data, hyp, rows):
+    """max_g of row i's latent leave-one-out variance over sf2_g among `rows`, each from a factorisation of the other
+    rows (nothing shared with the recursion): sf2 - k_i^T (K_-i + sn2 I)^-1 k_i."""
+    out = np.zeros((len(data), len(rows)), dtype=LD)
+    for g, (dg, (sf2, sn2)) in enumerate(zip(data, hyp)):
+        X = dg["X"][rows]
+        for i in range(len(rows)):
+            rest = np.delete(np.arange(len(rows)), i)
+            K = R.kernel_ld(X[rest], dg["ell"], sf2, X[rest]) + LD(sn2) * np.eye(len(rest), dtype=LD)
+            v = A.solve_lower_ld(A.chol_ld(K), R.kernel_ld(X[rest], dg["ell"], sf2, X[i:i + 1]).T.copy())
+            out[g, i] = (LD(sf2) - (v * v).sum()) / LD(sf2)
+    return out.max(0)
+
+
+def test_three_gp_scores_are_the_leave_one_out_variances_with_each_gps_own_noise():
+    c = DR.model_red_case()
+    ref, n = c["ref"], DR.M_RED_N
+    cond = max(n * sf2 / sn2 for sf2, sn2 in c["hyp"])
+    for t in (0, 16):   # the start, and with 16 rows gone
+        rows = np.flatnonzero(~np.isnan(ref["tables"][t].astype(np.float64)))
+        assert len(rows) == n - t
+        want = _loo_scores(c["data"], c["hyp"], rows)
+        rel = float(np.abs(ref["tables"][t][rows] / want - 1).max())
+        print(f"[redundant quad3d loo] step {t}: worst relative difference {rel:.3e}")
+        # longdouble evaluations of a quantity whose condition is that of K + sn2 I (the bound of the test above)
+        assert rel <= 64 * n * cond * float(np.finfo(LD).eps), rel
+
+
+@pytest.mark.parametrize("inert", [False, True], ids=["every row live", "a row inert in one GP"])
+@pytest.mark.parametrize("m", [17, 33])
+def test_every_gp_decides_a_pick_of_the_three_gp_cases(m, inert):
+    """Each GP's term is the score of at least one picked row, by more than the model's score error both ways, and the
+    picks change when it is left out and when the loop reads GP 0's outputscale and noise for it: a device kernel with
+    either defect cannot give the model's picks.  (m = 1 is a prefix of these runs.)"""
+    c = DR.model_red_case(inert=inert)
+    ref, model = c["ref"], c["model"]
+    picks = ref["picks"][:m].tolist()
+    err = max(DR.score_error(model["tables"][t], ref["tables"][t]) for t in range(m))
+    decided = DR.red_decided_by(c["Ps"], c["hyp"], c["live"], picks, err)
+    print(f"[redundant decides] m {m} inert {inert}: steps decided per GP {[len(d) for d in decided]}, first {[d[:1] for d in decided]}")
+    for g in range(3):
+        assert decided[g], (m, inert, g)
+        rest = [q for q in range(3) if q != g]
+        without = DR.redundant_ld([c["Ps"][q] for q in rest], [c["hyp"][q] for q in rest], m, live=[c["live"][q] for q in rest])
+        assert without["picks"].tolist() != picks, (m, inert, g)
+        if g:
+            hyp = list(c["hyp"])
+            hyp[g] = hyp[0]
+            assert DR.redundant_ld(c["Ps"], hyp, m, live=c["live"])["picks"].tolist() != picks, (m, inert, g)
 
 
 def _posterior_var_ld(X, ell, Z):
