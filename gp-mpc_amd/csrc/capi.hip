@@ -2432,4 +2432,101 @@ gpmpc_status gpmpc_rollout(gpmpc_handle* h, int32_t P, int32_t T, const double* 
     return GPMPC_OK;
 }
 
+gpmpc_status gpmpc_rollout_lin(gpmpc_handle* h, int32_t P, int32_t T, const double* x0_dev, const double* u_dev,
+                               int32_t with_gp, double* x_dev, double* A_dev, double* B_dev, double* var_dev,
+                               const double* K, const double* cov0_dev, int32_t with_noise, double* cov_dev) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    const int nx = h->md.nx, nu = h->md.nu;
+    const char* bad = nullptr;
+    if (P < 1 || T < 1) bad = "no trajectories or no steps (P, T >= 1)";
+    else if (!x0_dev || !u_dev || !x_dev) bad = "null array (x0_dev, u_dev and x_dev are required)";
+    else if (!A_dev || !B_dev) bad = "null array (A_dev and B_dev are required)";
+    else if (with_gp != 0 && with_gp != 1) bad = "with_gp must be 0 or 1";
+    else if (with_noise != 0 && with_noise != 1) bad = "with_noise must be 0 or 1";
+    else if ((int64_t)P * ((int64_t)T + 1) * nx > INT32_MAX) bad = "P (T + 1) nx does not fit an int32";
+    else if ((int64_t)P * (int64_t)T * nx * nx > INT32_MAX) bad = "P T nx nx does not fit an int32";
+    if (!bad && K)
+        for (int i = 0; i < nu * nx; ++i)
+            if (!std::isfinite(K[i])) bad = "K has a non-finite entry";
+    if (bad) return fail(GPMPC_ERR_ARG, bad);
+    if (!h->model_set) return fail(GPMPC_ERR_STATE, "the prior parameters are not set (gpmpc_set_model first)");
+    const int ngp = h->md.ngp;
+    if (with_gp) {
+        if (!h->P.use_gp) return fail(GPMPC_ERR_STATE, "with_gp = 1 while the handle's GPs are off (gpmpc_use_gp)");
+        for (int g = 0; g < ngp; ++g)
+            if (!h->gp[g].set) return fail(GPMPC_ERR_STATE, "GP " + std::to_string(g) + " not set");
+    }
+    const bool want_var = var_dev || cov_dev;
+    if (want_var)
+        for (int g = 0; g < ngp; ++g) {
+            if (!h->gp[g].set) return fail(GPMPC_ERR_STATE, "the variance needs GP " + std::to_string(g) + ", which is not set");
+            if (!h->gp[g].linvT) return fail(GPMPC_ERR_STATE, "the variance needs Linv (GP " + std::to_string(g) + " has none)");
+        }
+    (void)hipSetDevice(h->device);
+    size_t D = 0;
+    for (int g = 0; g < ngp; ++g) D += h->md.gp_dim[g];
+    // the gathered variance inputs, and behind them the variances themselves when the caller takes none
+    const size_t gathered = want_var ? (size_t)P * T * D : 0;
+    const size_t need = gathered + (cov_dev && !var_dev ? (size_t)P * T * ngp : 0);
+    if (need > h->roll_doubles) {   // (before anything is queued: a failed allocation leaves the handle as it was)
+        const gpmpc_status got = replace_scratch(&h->roll, need);
+        if (got != GPMPC_OK) return got;
+        h->roll_doubles = need;
+    }
+    HIPCHK(ensure_side(h));
+    hipStream_t s = h->side;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    RolloutLinArgs a{};
+    for (int i = 0; i < kMaxParams; ++i) a.r.params[i] = h->P.params[i];
+    a.r.dt = h->P.dt;
+    a.r.P = P;
+    a.r.T = T;
+    a.r.x0 = x0_dev;
+    a.r.u = u_dev;
+    a.r.x = x_dev;
+    a.A = A_dev;
+    a.B = B_dev;
+    if (with_gp)
+        for (int g = 0; g < ngp; ++g) a.r.gp[g] = h->P.gp[g];
+    HIPCHK(launch_rollout_lin(h->model, a, with_gp != 0, s));
+    if (want_var) {
+        // gpmpc_rollout's gather and variance launches, statement by statement
+        double* var = var_dev ? var_dev : h->roll + gathered;
+        HIPCHK(launch_rollout_inputs(h->model, x_dev, u_dev, P, T, h->roll, s));
+        for (int g = 0, col = 0; g < ngp; col += h->md.gp_dim[g], ++g) {
+            PostArgs pa{};
+            pa.Z = h->roll + col;
+            pa.ldz = (int)D;
+            pa.P = P * T;
+            pa.d = h->md.gp_dim[g];
+            pa.with_noise = 0;
+            pa.var = var;
+            pa.var_stride = ngp;
+            pa.var_off = g;
+            HIPCHK(launch_gp_post(h->P.gp[g], h->gp[g].npad, pa, false, s, h->var_trim ? 0 : 1));
+        }
+        if (cov_dev) {
+            RolloutCovArgs c{};
+            c.dt = h->P.dt;
+            c.P = P;
+            c.T = T;
+            c.closed = K ? 1 : 0;
+            if (K)
+                for (int i = 0; i < nu * nx; ++i) c.K[i] = K[i];
+            for (int g = 0; g < ngp; ++g) c.noise[g] = with_noise ? h->P.gp[g].sn2 : 0.0;
+            c.x = x_dev;
+            c.u = u_dev;
+            c.A = A_dev;
+            c.B = B_dev;
+            c.var = var;
+            c.cov0 = cov0_dev;
+            c.cov = cov_dev;
+            HIPCHK(launch_rollout_cov(h->model, c, s));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return GPMPC_OK;
+}
+
 }  // extern "C"

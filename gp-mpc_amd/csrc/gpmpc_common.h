@@ -639,6 +639,32 @@ struct RolloutArgs {
 hipError_t launch_rollout(int model, const RolloutArgs& a, bool with_gp, hipStream_t stream);
 // Z [P T][D]: the GP inputs z_k[gp_src_g] along x [P][T+1][nx], u [P][T][nu], D = sum of the GPs' dimensions
 hipError_t launch_rollout_inputs(int model, const double* x, const double* u, int P, int T, double* Z, hipStream_t stream);
+// The same rollout with the Jacobians of every step (sqp_kernel.hip rollout_lin_kernel; gpmpc_rollout_lin fills it):
+// A [P][T][nx][nx] and B [P][T][nx][nu], row-major, the exact derivative of the RK4 step at (x_k, u_k).
+struct RolloutLinArgs {
+    RolloutArgs r;
+    double* A;
+    double* B;
+};
+hipError_t launch_rollout_lin(int model, const RolloutLinArgs& a, bool with_gp, hipStream_t stream);
+// The state covariance along a finished rollout (rollout_cov.hip; gpmpc_rollout_lin fills it), by value:
+//   S_0 = cov0 or zero,  S_{k+1} = Phi_k S_k Phi_k^T + Bd diag(q_k) Bd^T,  Phi_k = A_k + B_k K (A_k: open loop),
+//   q_k[j] = dt^2 sum_g W_{j,g}(x_k, u_k) (var[p][k][g] + noise[g])     (Model::var_weights, Bd = Model::unc)
+struct RolloutCovArgs {
+    double dt;
+    int32_t P, T;
+    int32_t closed;              // K is read (0: Phi_k = A_k)
+    double K[kMaxNU * kMaxNX];   // [nu][nx] row-major
+    double noise[kMaxGP];        // with_noise * sn2_g
+    const double* x;             // [P][T+1][nx]
+    const double* u;             // [P][T][nu]
+    const double* A;             // [P][T][nx][nx]
+    const double* B;             // [P][T][nx][nu]
+    const double* var;           // [P][T][n_gp]
+    const double* cov0;          // [P][nx][nx] or null
+    double* cov;                 // [P][T+1][nx][nx]
+};
+hipError_t launch_rollout_cov(int model, const RolloutCovArgs& a, hipStream_t stream);
 hipError_t launch_gp_post(const GPDev& g, int npad, const PostArgs& a, bool from_state, hipStream_t stream,
                           int var_full = 0);   // PostBatch::var_full
 hipError_t launch_gp_post_batch(const PostBatch& pb, bool from_state, hipStream_t stream);

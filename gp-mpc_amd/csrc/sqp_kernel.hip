@@ -4088,6 +4088,191 @@ hipError_t launch_rollout_inputs(int model, const double* x, const double* u, in
     return hipGetLastError();
 }
 
+// A copy of v the optimiser cannot trace back: expressions over copies are not merged with those over the originals.
+__device__ __forceinline__ double opaque_copy(double v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+// The rollout with the Jacobians of every step (gpmpc_rollout_lin): the states by rollout_kernel's statements, and
+// beside them A_k = dx_{k+1}/dx_k, B_k = dx_{k+1}/du_k, the exact derivative of the RK4 step (linearize's tangent
+// recursion: dk_s = df/dx (E + c_s dt dk_{s-1}) + [0, df/du] through Model::tangent, in lockstep with the substages,
+// so no substage state is kept).  Both variants keep the 16-trajectories-per-wavefront tile: the four 16-lane rows
+// integrate the same states, and row r carries the tangent columns r CB .. r CB + CB - 1 of [A_k B_k], CB =
+// ceil((NX + NU) / 4) (a column past NX + NU - 1 is a zero column nobody stores: cartpole's last row has two).
+//   GP = true:  rollout_kernel's tile pass, once per GP and substage; it leaves S1..S3 beside S0 in out[.][4], and the
+//               input gradient sf2/ell^2 (S_{1+d} - (z_d - xbar_d) S0) is read from the same pass as the mean.
+//   GP = false: means and gradients are the constant zero.
+// The tangent is evaluated on opaque copies of the substage state, input and means: M::f then stands alone in the
+// optimiser's view exactly as in rollout_kernel (no product shared with the tangent, so the same contractions), and
+// the states are that kernel's bits.  Lanes 0..15 store the states; every lane of a live trajectory stores its columns.
+template <int ID, bool GP>
+__global__ __launch_bounds__(64) void rollout_lin_kernel(RolloutLinArgs b) {
+    using M = Model<ID>;
+    constexpr int NX = M::NX, NU = M::NU, NGP = M::NGP, NB = NX + NU, CB = (NB + 3) / 4;
+    const RolloutArgs& a = b.r;
+    // quad3d with GPs: V, dk and the accumulator dF at 12 x 4 columns a lane pass the 512 registers next to the tile
+    // pass, so dF, touched once a substage, lives in LDS there ([entry][lane]: a lane's own slots, conflict-free)
+    constexpr bool kLdsDF = GP && NX * CB >= 48;
+    __shared__ double zb[GP ? NGP * 16 * 4 : 1], czz[GP ? NGP * 16 : 1], out[GP ? NGP * 16 * 4 : 1];
+    __shared__ double dfl[kLdsDF ? NX * CB * 64 : 1];
+    const int lane = threadIdx.x;
+    const int p = blockIdx.x * 16 + (lane & 15);
+    const bool live = p < a.P, store = live && lane < 16;
+    const size_t tr = (size_t)min(p, a.P - 1);
+    const int j0 = (lane >> 4) * CB;
+    const double* u = a.u + tr * a.T * NU;
+    double* x = a.x + tr * (a.T + 1) * NX;
+    double* Ao = b.A + tr * a.T * NX * NX;
+    double* Bo = b.B + tr * a.T * NX * NU;
+    double pv[kMaxParams];
+#pragma unroll
+    for (int i = 0; i < kMaxParams; ++i) pv[i] = a.params[i];
+    const double dt = a.dt;
+    double xs[NX], us[NU], k[NX], acc[NX], xi[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xs[i] = a.x0[tr * NX + i];
+    if (store) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) x[i] = xs[i];
+    }
+    const double cs[4] = {0.0, 0.5, 0.5, 1.0}, ws[4] = {1.0, 2.0, 2.0, 1.0};
+    for (int step = 0; step < a.T; ++step) {
+#pragma unroll
+        for (int c = 0; c < NU; ++c) us[c] = u[(size_t)step * NU + c];
+        double gm[kMaxGP] = {0.0, 0.0, 0.0, 0.0};
+        double gt[kMaxGP] = {0.0, 0.0, 0.0, 0.0};   // the means again, for the tangent
+        double gg[NGP][3];
+#pragma unroll
+        for (int g = 0; g < NGP; ++g) gg[g][0] = gg[g][1] = gg[g][2] = 0.0;
+        double V[NX][CB], dk[NX][CB], dF[NX][CB];
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+#pragma unroll
+            for (int j = 0; j < CB; ++j) {
+                V[i][j] = (i == j0 + j) ? 1.0 : 0.0;
+                if constexpr (kLdsDF) dfl[(i * CB + j) * 64 + lane] = V[i][j];
+                else dF[i][j] = V[i][j];
+            }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) xi[i] = (s == 0) ? xs[i] : fma(cs[s] * dt, k[i], xs[i]);
+            if constexpr (GP) {
+                static_for<NGP>([&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    if (s > 0 && !M::gp_state_dep[G]) return;
+                    const GPDev& g = a.gp[G];
+                    double zc[3];
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        const int src = M::gp_src[G][d];
+                        zc[d] = d < M::gp_dim[G] ? (src < NX ? xi[src] : us[src - NX]) - g.xbar[d] : 0.0;
+                    }
+                    if (lane < 16) {
+                        double* dst = zb + (G * 16 + lane) * 4;
+                        dst[0] = zc[0];
+                        dst[1] = zc[1];
+                        dst[2] = zc[2];
+                        dst[3] = 1.0;
+                        czz[G * 16 + lane] = -0.5 * g.inv_ell2 * fma(zc[0], zc[0], fma(zc[1], zc[1], zc[2] * zc[2]));
+                    }
+                });
+                __syncthreads();
+                static_for<NGP>([&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    if (s > 0 && !M::gp_state_dep[G]) return;
+                    const GPDev& g = a.gp[G];
+                    gp_tiles_dispatch(g.tX, g.tW, g.ntile, zb + G * 64, czz + G * 16, out + G * 64, lane, 1);
+                });
+                __syncthreads();
+                static_for<NGP>([&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    if (s > 0 && !M::gp_state_dep[G]) return;
+                    const GPDev& g = a.gp[G];
+                    gm[G] = a.gp[G].sf2 * out[(G * 16 + (lane & 15)) * 4];
+                    // the gradient of the same sums (eval_gps step 3), at the point the lane wrote
+                    const double* o = out + (G * 16 + (lane & 15)) * 4;
+                    const double s0 = o[0], gs = g.sf2 * g.inv_ell2;
+                    // the tangent's mean is a product of its own: a second use of gm's would keep it out of M::f's fma
+                    gt[G] = g.sf2 * opaque_copy(s0);
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        const int src = M::gp_src[G][d];
+                        const double zc = d < M::gp_dim[G] ? (src < NX ? xi[src] : us[src - NX]) - g.xbar[d] : 0.0;
+                        gg[G][d] = d < M::gp_dim[G] ? gs * fma(-zc, s0, o[1 + d]) : 0.0;
+                    }
+                });
+            }
+            M::f(pv, xi, us, gm, k);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) acc[i] = (s == 0) ? k[i] : fma(ws[s], k[i], acc[i]);
+            // the tangent of this substage on this lane's columns
+            double xt[NX], ut[NU];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) xt[i] = opaque_copy(xi[i]);
+#pragma unroll
+            for (int c = 0; c < NU; ++c) ut[c] = opaque_copy(us[c]);
+            M::template tangent<CB>(pv, xt, ut, gt, gg, V, j0, dk);
+            const double cn = (s < 3) ? cs[s + 1] * dt : 0.0;
+#pragma unroll
+            for (int i = 0; i < NX; ++i)
+#pragma unroll
+                for (int j = 0; j < CB; ++j) {
+                    if constexpr (kLdsDF) {
+                        double* d = dfl + (i * CB + j) * 64 + lane;
+                        *d = fma(dt / 6.0 * ws[s], dk[i][j], *d);
+                    } else {
+                        dF[i][j] = fma(dt / 6.0 * ws[s], dk[i][j], dF[i][j]);
+                    }
+                    V[i][j] = fma(cn, dk[i][j], (i == j0 + j) ? 1.0 : 0.0);
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < NX; ++i) xs[i] = fma(dt / 6.0, acc[i], xs[i]);
+        if (store) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) x[(size_t)(step + 1) * NX + i] = xs[i];
+        }
+        if constexpr (kLdsDF) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i)
+#pragma unroll
+                for (int j = 0; j < CB; ++j) dF[i][j] = dfl[(i * CB + j) * 64 + lane];
+        }
+        if (live) {
+            double* Ak = Ao + (size_t)step * NX * NX;
+            double* Bk = Bo + (size_t)step * NX * NU;
+#pragma unroll
+            for (int i = 0; i < NX; ++i)
+#pragma unroll
+                for (int j = 0; j < CB; ++j) {
+                    const int col = j0 + j;
+                    if (col < NX) Ak[i * NX + col] = dF[i][j];
+                    else if (col < NB) Bk[i * NU + col - NX] = dF[i][j];
+                }
+        }
+    }
+}
+
+template <int ID>
+static hipError_t launch_rollout_lin_of(const RolloutLinArgs& a, bool with_gp, hipStream_t stream) {
+    if (with_gp)
+        hipLaunchKernelGGL((rollout_lin_kernel<ID, true>), dim3((a.r.P + 15) / 16), dim3(64), 0, stream, a);
+    else
+        hipLaunchKernelGGL((rollout_lin_kernel<ID, false>), dim3((a.r.P + 15) / 16), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_rollout_lin(int model, const RolloutLinArgs& a, bool with_gp, hipStream_t stream) {
+    switch (model) {
+        case kQuad2D: return launch_rollout_lin_of<kQuad2D>(a, with_gp, stream);
+        case kQuad3D: return launch_rollout_lin_of<kQuad3D>(a, with_gp, stream);
+        case kCartpole: return launch_rollout_lin_of<kCartpole>(a, with_gp, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
 // LINEAR_LS stage costs of the stored solution (gpmpc_set_cost_buffer), one thread per (instance,
 // stage), queued right behind the SQP launch: cost[b][k] = 1/2 ||y_k - y_ref,k||^2_W, y = [x; u],
 // W = dt blkdiag(Q, R) on stages 0..H-1 and Q on stage H (gpmpc.py:231-239, mpc.py:101-102, acados

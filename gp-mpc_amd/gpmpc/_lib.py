@@ -21,7 +21,7 @@ LIB_PATH = Path(os.environ.get("GPMPC_LIB", _DEFAULT_LIB))
 CSRC = Path(__file__).resolve().parents[1] / "csrc"
 # the files gpmpc_build_id's source hash covers, in the Makefile's order (HASHED)
 HASHED = ["sqp_kernel.hip", "gp_kernels.hip", "gp_append.hip", "gp_drop.hip", "gp_refactor.hip", "gp_fit.hip",
-          "gp_love.hip", "gp_fitc.hip", "gp_observe.hip", "capi.hip", "gpmpc_common.h", "gp_tile.h", "gp_pick.h",
+          "gp_love.hip", "gp_fitc.hip", "gp_observe.hip", "rollout_cov.hip", "capi.hip", "gpmpc_common.h", "gp_tile.h", "gp_pick.h",
           "models.h", "../../include/gpmpc_mi355x.h", "build_id.cpp", "Makefile"]
 
 _lib = None
@@ -64,6 +64,7 @@ SIGNATURES = {
     "gpmpc_gp_posterior": (_I, [_I, _I, _I, _P, _P, _D, _D, _D, _P, _I, _P, _P, _I, _P]),
     "gpmpc_plant_step": (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout": (_I, [_P, _I, _I, _P, _P, _I, _P, _P]),
+    "gpmpc_rollout_lin": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "gpmpc_preprocess": (_I, [_P, _I, _P, _P, _P, _I, _P, _D, _D, _P, _P, _P]),
     "gpmpc_gp_informative": (_I, [_P, _I, _P, _P, _I, _P, _P, _P]),
     "gpmpc_gp_select": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),

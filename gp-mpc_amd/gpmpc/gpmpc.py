@@ -629,14 +629,26 @@ class GPMPC:
                 raise AssertionError(f"instance {i}: unexpected status {int(self.solver.status[i])}")
         return u0
 
-    def predict_trajectory(self, x0, u, with_gp: bool = True, return_var: bool = False):
+    def predict_trajectory(self, x0, u, with_gp: bool = True, return_var: bool = False, return_cov: bool = False,
+                           feedback=None, with_noise: bool = False):
         """What the controller believes will happen: the open-loop rollout of its model from ``x0`` under the
         inputs ``u`` (``BatchSolver.rollout``), the learned GP means included unless ``with_gp=False`` (the prior
         alone).  numpy in and out: one trajectory, ``x0`` (nx,) and ``u`` (T, nu), gives (T+1, nx); a batch,
         (P, nx) and (P, T, nu), gives (P, T+1, nx).  ``return_var=True`` adds the GPs' posterior variances along
-        it, (T, n_gp) or (P, T, n_gp).  The GPs must be uploaded (``reset()`` after ``train_gp``)."""
+        it, (T, n_gp) or (P, T, n_gp).  ``return_cov=True`` adds, last, the state covariance the model itself
+        states along the prediction (``BatchSolver.rollout_lin``), (T+1, nx, nx) or (P, T+1, nx, nx), from zero at
+        ``x0``: ``feedback=None`` propagates through the open loop's ``A_k``, ``feedback="lqr"`` through
+        ``A_k + B_k K`` with the controller's ``lqr_gain`` (the tightening's assumption), an array is taken as
+        ``K`` (nu, nx); ``with_noise=True`` adds the GPs' likelihood noise to their variances, once.  The GPs must
+        be uploaded (``reset()`` after ``train_gp``)."""
         assert not (with_gp and getattr(self, "_requires_recompile", False)), "GP model must be uploaded (call reset())"
-        return predict_trajectory(self.solver, x0, u, with_gp=with_gp, return_var=return_var)
+        if not return_cov:
+            return predict_trajectory(self.solver, x0, u, with_gp=with_gp, return_var=return_var)
+        K = self.lqr_gain if isinstance(feedback, str) and feedback == "lqr" else feedback
+        if isinstance(K, str):
+            raise ValueError('feedback is None, "lqr" or a gain (nu, nx)')
+        return predict_trajectory(self.solver, x0, u, with_gp=with_gp, return_var=return_var, return_cov=True,
+                                  feedback=K, with_noise=with_noise)
 
     def reference_trajectory(self) -> np.ndarray:
         """`gpmpc/gpmpc.py:509-514`."""

@@ -210,6 +210,17 @@ def prediction_error(ctrl, data: dict, horizon: int, stride: int = 1, with_gp: b
     ``ctrl.solver.rollout`` call (P = windows x B).  Returns (horizon, nx): the root mean square over windows and
     instances of ``x_pred[k] - obs[s + k]``, k = 1 .. horizon.  ``with_gp=False`` gives the prior's curve to set
     beside the learned model's."""
+    x0, u, want = _prediction_windows(data, horizon, stride)
+    solver = ctrl.solver
+    x = solver.rollout(torch.as_tensor(np.ascontiguousarray(x0), device=solver.device),
+                       torch.as_tensor(np.ascontiguousarray(u), device=solver.device), with_gp=with_gp)
+    err = x.cpu().numpy()[:, 1:] - want[:, 1:]
+    return np.sqrt((err ** 2).mean(axis=0))
+
+
+def _prediction_windows(data: dict, horizon: int, stride: int):
+    """The windows of :func:`prediction_error`: x0 (W B, nx), u (W B, horizon, nu) and the recorded states
+    (W B, horizon+1, nx), window-major, then instance."""
     obs = np.asarray(data["obs"], dtype=np.float64)
     act = np.asarray(data["action"], dtype=np.float64)
     S, B = act.shape[:2]
@@ -223,11 +234,30 @@ def prediction_error(ctrl, data: dict, horizon: int, stride: int = 1, with_gp: b
     x0 = obs[starts].reshape(len(starts) * B, -1)                                    # window-major, then instance
     u = act[steps[:, :horizon]].transpose(0, 2, 1, 3).reshape(len(starts) * B, horizon, -1)
     want = obs[steps].transpose(0, 2, 1, 3).reshape(len(starts) * B, horizon + 1, -1)
+    return x0, u, want
+
+
+def prediction_calibration(ctrl, data: dict, horizon: int, stride: int = 1, feedback=None) -> np.ndarray:
+    """Whether the model's own uncertainty matches its multi-step error on a recorded run.  The windows are
+    :func:`prediction_error`'s, rolled out in one ``ctrl.solver.rollout_lin`` call with the state covariance
+    propagated from zero and the likelihood noise included (``with_noise=True``); ``feedback`` is None (open loop),
+    ``"lqr"`` (the controller's ``lqr_gain``) or a gain (nu, nx).  Returns (horizon, nx): the root mean square over
+    windows and instances of ``(x_pred[k] - obs[s + k]) / sqrt(diag Sigma_k)``, k = 1 .. horizon.  Values near 1 mean
+    calibrated uncertainty, above 1 overconfidence.  A state whose predicted variance is 0 somewhere (one the
+    uncertainty has not reached yet) gives NaN at that step."""
+    x0, u, want = _prediction_windows(data, horizon, stride)
     solver = ctrl.solver
-    x = solver.rollout(torch.as_tensor(np.ascontiguousarray(x0), device=solver.device),
-                       torch.as_tensor(np.ascontiguousarray(u), device=solver.device), with_gp=with_gp)
-    err = x.cpu().numpy()[:, 1:] - want[:, 1:]
-    return np.sqrt((err ** 2).mean(axis=0))
+    K = ctrl.lqr_gain if isinstance(feedback, str) and feedback == "lqr" else feedback
+    if isinstance(K, str):
+        raise ValueError('feedback is None, "lqr" or a gain (nu, nx)')
+    out = solver.rollout_lin(torch.as_tensor(np.ascontiguousarray(x0), device=solver.device),
+                             torch.as_tensor(np.ascontiguousarray(u), device=solver.device), cov=True, K=K,
+                             with_noise=True)
+    err = out["x"].cpu().numpy()[:, 1:] - want[:, 1:]
+    var = np.diagonal(out["cov"].cpu().numpy()[:, 1:], axis1=-2, axis2=-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z2 = np.where(var > 0.0, err ** 2 / var, np.nan)
+    return np.sqrt(z2.mean(axis=0))
 
 
 def learn(n_epochs: int, ctrl, lr: float, gp_iterations: int, seed: int, samples_per_epoch: int,
@@ -239,7 +269,8 @@ def learn(n_epochs: int, ctrl, lr: float, gp_iterations: int, seed: int, samples
 
     ``report_prediction=h > 0``: every epoch's test run also records :func:`prediction_error` at horizon h on
     itself, the learned model's curve and the prior's, under the key ``"prediction_error"`` of its dict:
-    ``{"gp": (h, nx), "prior": (h, nx)}``.  Off by default, which leaves the returned runs as they were."""
+    ``{"gp": (h, nx), "prior": (h, nx)}``, and beside it :func:`prediction_calibration` of the learned model (open
+    loop) under the key ``"calibration"``, (h, nx).  Off by default, which leaves the returned runs as they were."""
     from . import distributed as D
 
     spec = ctrl.model
@@ -274,6 +305,7 @@ def learn(n_epochs: int, ctrl, lr: float, gp_iterations: int, seed: int, samples
             test_runs[epoch]["prediction_error"] = {
                 "gp": prediction_error(ctrl, test_runs[epoch], report_prediction),
                 "prior": prediction_error(ctrl, test_runs[epoch], report_prediction, with_gp=False)}
+            test_runs[epoch]["calibration"] = prediction_calibration(ctrl, test_runs[epoch], report_prediction)
         timing[epoch] = {"train_gp": t4 - t3, "test": t5 - t4, "collect": t6 - t5, "n_train": len(x_train)}
     return train_runs, test_runs, timing
 

@@ -52,10 +52,13 @@ def _c(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
-def predict_trajectory(solver, x0, u, with_gp: bool = True, return_var: bool = False):
+def predict_trajectory(solver, x0, u, with_gp: bool = True, return_var: bool = False, return_cov: bool = False,
+                       feedback=None, with_noise: bool = False):
     """numpy front of ``solver.rollout`` (``GPMPC.predict_trajectory`` / ``MPC.predict_trajectory``): one trajectory,
     ``x0`` (nx,) and ``u`` (T, nu), gives ``x`` (T+1, nx); a batch, (P, nx) and (P, T, nu), gives (P, T+1, nx).  With
-    ``return_var`` also the GP variances (T, n_gp) / (P, T, n_gp)."""
+    ``return_var`` also the GP variances (T, n_gp) / (P, T, n_gp).  With ``return_cov`` (``solver.rollout_lin``) the
+    state covariance (T+1, nx, nx) / (P, T+1, nx, nx) comes last, propagated from zero with ``feedback`` as the gain
+    ``K`` (nu, nx) or None for the open loop, and the likelihood noise added when ``with_noise``."""
     x0 = np.asarray(x0, dtype=np.float64)
     u = np.asarray(u, dtype=np.float64)
     single = x0.ndim == 1
@@ -66,12 +69,17 @@ def predict_trajectory(solver, x0, u, with_gp: bool = True, return_var: bool = F
     elif x0.ndim != 2 or u.ndim != 3 or u.shape[0] != x0.shape[0]:
         raise ValueError("a batch takes x0 (P, nx) and u (P, T, nu)")
     dev = solver.device
-    out = solver.rollout(torch.as_tensor(np.ascontiguousarray(x0), device=dev),
-                         torch.as_tensor(np.ascontiguousarray(u), device=dev), with_gp=with_gp, var=return_var)
-    out = tuple(t.cpu().numpy() for t in (out if return_var else (out,)))
+    x0t, ut = torch.as_tensor(np.ascontiguousarray(x0), device=dev), torch.as_tensor(np.ascontiguousarray(u), device=dev)
+    if return_cov:
+        res = solver.rollout_lin(x0t, ut, with_gp=with_gp, var=return_var, cov=True, K=feedback, with_noise=with_noise)
+        out = (res["x"],) + ((res["var"],) if return_var else ()) + (res["cov"],)
+    else:
+        out = solver.rollout(x0t, ut, with_gp=with_gp, var=return_var)
+        out = out if return_var else (out,)
+    out = tuple(t.cpu().numpy() for t in out)
     if single:
         out = tuple(a[0] for a in out)
-    return out if return_var else out[0]
+    return out if return_var or return_cov else out[0]
 
 
 class BatchSolver:
@@ -743,3 +751,45 @@ class BatchSolver:
         _lib.check(self.lib.gpmpc_rollout(self._h, P, T, x0.data_ptr(), u.data_ptr(), int(bool(with_gp)), x.data_ptr(),
                                           _lib.ptr(v)))
         return (x, v) if var else x
+
+    def rollout_lin(self, x0: torch.Tensor, u: torch.Tensor, with_gp: bool = True, var: bool = False, cov: bool = False,
+                    K=None, cov0: torch.Tensor | None = None, with_noise: bool = False) -> dict:
+        """:meth:`rollout` with the Jacobians of every step (gpmpc_rollout_lin).  Returns a dict: ``x`` (P, T+1, nx)
+        and, with ``var=True``, ``var`` (P, T, n_gp), both the bits :meth:`rollout` returns; ``A`` (P, T, nx, nx) and
+        ``B`` (P, T, nx, nu), the exact derivative of the RK4 step at ``(x_k, u_k)``, GP input gradients included
+        unless ``with_gp=False``.  With ``cov=True`` also ``cov`` (P, T+1, nx, nx): ``cov[:, 0]`` is ``cov0``
+        (P, nx, nx; None: zero) and ``cov[:, k+1] = Phi_k cov[:, k] Phi_k^T + Bd diag(q_k) Bd^T`` with
+        ``Phi_k = A_k + B_k K`` (``K`` (nu, nx), host; None: the open loop) and ``q_k`` the GP variances at
+        ``(x_k, u_k)`` (plus the likelihood noise with ``with_noise=True``, once) under the tightening's weights.
+        The variance and the covariance need every GP set with its Linv.  Synchronises the current stream first,
+        as :meth:`rollout` does, and returns with its work completed."""
+        x0 = x0.to(self.device, torch.float64).contiguous()
+        u = u.to(self.device, torch.float64).contiguous()
+        if x0.ndim != 2 or x0.shape[1] != self.nx:
+            raise ValueError(f"x0 must be (P, nx={self.nx})")
+        if u.ndim != 3 or u.shape[0] != x0.shape[0] or u.shape[2] != self.nu:
+            raise ValueError(f"u must be (P={x0.shape[0]}, T, nu={self.nu})")
+        P, T = int(u.shape[0]), int(u.shape[1])
+        if K is not None:
+            K = _c(K)
+            if K.shape != (self.nu, self.nx):
+                raise ValueError(f"K must be (nu={self.nu}, nx={self.nx})")
+        if cov0 is not None:
+            cov0 = cov0.to(self.device, torch.float64).contiguous()
+            if tuple(cov0.shape) != (P, self.nx, self.nx):
+                raise ValueError(f"cov0 must be (P={P}, nx={self.nx}, nx={self.nx})")
+
+        def new(*shape):
+            return torch.empty(*shape, dtype=torch.float64, device=self.device)
+
+        out = {"x": new(P, T + 1, self.nx), "A": new(P, T, self.nx, self.nx), "B": new(P, T, self.nx, self.nu)}
+        if var:
+            out["var"] = new(P, T, self.spec.n_gp)
+        if cov:
+            out["cov"] = new(P, T + 1, self.nx, self.nx)
+        torch.cuda.current_stream(self.device).synchronize()
+        _lib.check(self.lib.gpmpc_rollout_lin(self._h, P, T, x0.data_ptr(), u.data_ptr(), int(bool(with_gp)),
+                                              out["x"].data_ptr(), out["A"].data_ptr(), out["B"].data_ptr(),
+                                              _lib.ptr(out.get("var")), None if K is None else K.ctypes.data,
+                                              _lib.ptr(cov0), int(bool(with_noise)), _lib.ptr(out.get("cov"))))
+        return out

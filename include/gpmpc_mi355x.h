@@ -28,6 +28,7 @@
  * handle's, behind the handle's last call whatever stream that was on, and the stream is drained before the call
  * returns.  Unlike gpmpc_gp_inducing it has device inputs of the caller's, and they are the caller's to order:
  * x0_dev and u_dev must be complete when the call is made; the outputs are complete when it returns.
+ * gpmpc_rollout_lin follows the same rule as gpmpc_rollout in every respect (cov0_dev is one more input of the caller's).
  * The library reads no environment variables: every option is an explicit call.
  */
 #ifndef GPMPC_MI355X_H
@@ -468,6 +469,40 @@ gpmpc_status gpmpc_plant_step(gpmpc_handle* h, int32_t batch, const double* para
  * (GPMPC_ERR_STATE). */
 gpmpc_status gpmpc_rollout(gpmpc_handle* h, int32_t P, int32_t T, const double* x0_dev, const double* u_dev,
                            int32_t with_gp, double* x_dev, double* var_dev);
+
+/* gpmpc_rollout with the Jacobians of every step and, on request, the state covariance along the trajectory
+ * (csrc/sqp_kernel.hip rollout_lin_kernel, csrc/rollout_cov.hip).  P, T, x0_dev, u_dev, with_gp, x_dev and var_dev
+ * are gpmpc_rollout's: x_dev and var_dev receive the bits that call writes (the same RK4 statements and tile sums,
+ * the same gather and variance launches; the variance carries no likelihood noise and ignores a LOVE root).
+ *   A_dev [P][T][nx][nx], B_dev [P][T][nx][nu], row-major: A_k = dx_{k+1}/dx_k and B_k = dx_{k+1}/du_k, the exact
+ *     derivative of the RK4 step at (x_k, u_k): the tangent recursion dk_s = J_s[:, :nx] (E + c_s dt dk_{s-1}) +
+ *     [0, J_s[:, nx:]] over the four substages, J_s the Jacobian of the residual dynamics with the GP input gradient
+ *     sf2/ell^2 (S_{1+d} - (z_d - xbar_d) S0) taken from the tile pass that yields the mean (a GP whose input is a
+ *     control is evaluated at substage 0 only).  With with_gp = 0 means and gradients are zero and nothing of the
+ *     GPs is read.
+ *   cov_dev [P][T+1][nx][nx], may be NULL: Sigma_0 = cov0_dev [P][nx][nx] (NULL: zero; taken as given, the caller
+ *     keeps it symmetric), Sigma_{k+1} = Phi_k Sigma_k Phi_k^T + Bd diag(q_k) Bd^T with Phi_k = A_k + B_k K (K a
+ *     HOST array [nu][nx], row-major; NULL: the open loop, Phi_k = A_k), Bd the identity columns of the model's
+ *     uncertain dimensions and q_k[j] = dt^2 sum_g W_{j,g}(x_k, u_k) (var_g,k + with_noise noise_g), W the
+ *     tightening's variance weights (quad3d's literal cos(phi) sin(theta)^2 included).  This is the tightening's
+ *     recursion (gpmpc/gpmpc.py:425-498) with the learned model's own A_k, B_k along the trajectory in place of the
+ *     prior's constant Ad, Bd.  THE NOISE ENTERS ONCE (with_noise = 1), not twice as in the reference's tightening,
+ *     whose variance already includes it before cov_noise adds it again.  K is read before the call returns and
+ *     travels by value.  Every Sigma_k equals its transpose bit for bit (one triangle is computed and mirrored), and
+ *     every sum has a fixed order.  var_dev may be NULL with cov_dev given: the variances then go to scratch of the
+ *     handle.
+ * Independence as for gpmpc_rollout: a trajectory's x, A, B, var and cov depend on its own (x0, u, cov0) and the
+ * handle only, whatever P is and wherever it sits in the batch; the first k rows of A and B and the first k+1 rows
+ * of cov of a T-step call are those of a k-step call; a non-finite input poisons only its own trajectory.
+ * THE CALL IS SYNCHRONOUS and takes no stream (see "Streams" above).  Scratch (the gathered variance inputs, and the
+ * variances when var_dev is NULL) is the handle's, allocated before anything is queued and kept; if the allocation
+ * fails the call returns GPMPC_ERR_NOMEM and the handle is unchanged.
+ * Refused with nothing written: everything gpmpc_rollout refuses; also A_dev or B_dev NULL, with_noise not 0 or 1,
+ * a non-finite entry of K, P T nx nx not representable in int32 (GPMPC_ERR_ARG); var_dev or cov_dev with a GP not
+ * set or set without Linv (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_rollout_lin(gpmpc_handle* h, int32_t P, int32_t T, const double* x0_dev, const double* u_dev,
+                               int32_t with_gp, double* x_dev, double* A_dev, double* B_dev, double* var_dev,
+                               const double* K, const double* cov0_dev, int32_t with_noise, double* cov_dev);
 
 /* GP training rows from transitions, on the device: GPMPC.preprocess_data of the build (the reference's
  * gpmpc/gpmpc.py:113-151) for the handle's model, csrc/gp_observe.hip.  x_dev [P][nx], u_dev [P][nu] and

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Timing of BatchSolver.rollout (gpmpc_rollout) beside the chain of plant steps.
+"""Timing of BatchSolver.rollout (gpmpc_rollout) beside the chain of plant steps, and of BatchSolver.rollout_lin
+(gpmpc_rollout_lin) beside the plain rollout.
 
 Times, between two device synchronisations, one call of each side on the same inputs (x0 from initial_states, u near
 u_eq):
@@ -10,6 +11,10 @@ u_eq):
     prior_var  rollout(with_gp=False, var=True)
     plant      T chained plant_step launches at the prior's parameters: the only comparable thing the library
                could do before, and what `prior` equals bit for bit
+    lin        rollout_lin(with_gp=True)           the states and the Jacobians A_k, B_k, one launch
+    lin_var    rollout_lin(var=True)               plus the gather and the variance launches
+    lin_cov    rollout_lin(cov=True, K=lqr, with_noise=True)   plus the covariance launch (variances in scratch)
+    lin_prior  rollout_lin(with_gp=False)          the prior's Jacobians
 
 The sides alternate in one process: `--repeats` rounds, each timing every side `--calls` times after `--warmup`
 untimed calls; a round's figure is the median over its calls.  Prints one JSON object: per side the median round's
@@ -34,7 +39,7 @@ for p in (ROOT / "gp-mpc_amd", ROOT):
     if str(p) not in sys.path:
         sys.path.insert(0, str(p))
 
-SIDES = ("gp", "gp_var", "prior", "prior_var", "plant")
+SIDES = ("gp", "gp_var", "prior", "prior_var", "plant", "lin", "lin_var", "lin_cov", "lin_prior")
 
 
 def main(argv=None):
@@ -56,7 +61,7 @@ def main(argv=None):
         raise SystemExit("rollout_ab.py measures on the GPU: no HIP device available")
     from gpmpc.gp import GaussianProcess
     from gpmpc.models import get_spec
-    from gpmpc.solver import BatchSolver
+    from gpmpc.solver import BatchSolver, setup_prior_dynamics
     from gpmpc.synthetic import DEFAULT_HYPERS, initial_states, make_training_data
 
     spec = get_spec(args.model)
@@ -85,6 +90,10 @@ def main(argv=None):
     side = {"gp": lambda: s.rollout(x0t, ut), "gp_var": lambda: s.rollout(x0t, ut, var=True),
             "prior": lambda: s.rollout(x0t, ut, with_gp=False), "prior_var": lambda: s.rollout(x0t, ut, with_gp=False, var=True),
             "plant": plant}
+    K = setup_prior_dynamics(*spec.prior_jacobian(np.zeros(spec.nx), spec.u_eq), np.diag(spec.q_diag), np.diag(spec.r_diag), spec.dt)[2]
+    side.update({"lin": lambda: s.rollout_lin(x0t, ut), "lin_var": lambda: s.rollout_lin(x0t, ut, var=True),
+                 "lin_cov": lambda: s.rollout_lin(x0t, ut, cov=True, K=K, with_noise=True),
+                 "lin_prior": lambda: s.rollout_lin(x0t, ut, with_gp=False)})
 
     def timed(fn):
         ms = []
@@ -98,6 +107,7 @@ def main(argv=None):
         return statistics.median(ms)
 
     assert torch.equal(s.rollout(x0t, ut, with_gp=False)[:, -1], plant()), "the prior rollout is the chain of plant steps"
+    assert torch.equal(s.rollout_lin(x0t, ut)["x"], s.rollout(x0t, ut)), "rollout_lin's states are the rollout's"
     rounds = {name: [] for name in args.sides}
     for _ in range(args.repeats):
         for name in args.sides:
