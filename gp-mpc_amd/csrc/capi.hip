@@ -2529,4 +2529,74 @@ gpmpc_status gpmpc_rollout_lin(gpmpc_handle* h, int32_t P, int32_t T, const doub
     return GPMPC_OK;
 }
 
+gpmpc_status gpmpc_rollout_sample(gpmpc_handle* h, int32_t P, int32_t T, const double* x0_dev, const double* u_dev,
+                                  const double* xref_dev, const double* K, int32_t clip, const double* xi_dev,
+                                  int32_t with_gp, int32_t with_noise, double* x_dev, double* uapp_dev,
+                                  double* var_dev) {
+    if (!h) return fail(GPMPC_ERR_ARG, "null handle");
+    const int nx = h->md.nx, nu = h->md.nu;
+    const char* bad = nullptr;
+    if (P < 1 || T < 1) bad = "no trajectories or no steps (P, T >= 1)";
+    else if (!x0_dev || !u_dev || !x_dev) bad = "null array (x0_dev, u_dev and x_dev are required)";
+    else if (with_gp != 0 && with_gp != 1) bad = "with_gp must be 0 or 1";
+    else if (with_noise != 0 && with_noise != 1) bad = "with_noise must be 0 or 1";
+    else if (clip != 0 && clip != 1) bad = "clip must be 0 or 1";
+    else if ((K != nullptr) != (xref_dev != nullptr)) bad = "K and xref_dev go together (both given, or both NULL)";
+    else if ((int64_t)P * ((int64_t)T + 1) * nx > INT32_MAX) bad = "P (T + 1) nx does not fit an int32";
+    if (!bad && K)
+        for (int i = 0; i < nu * nx; ++i)
+            if (!std::isfinite(K[i])) bad = "K has a non-finite entry";
+    if (bad) return fail(GPMPC_ERR_ARG, bad);
+    if (!h->model_set) return fail(GPMPC_ERR_STATE, "the prior parameters are not set (gpmpc_set_model first)");
+    const int ngp = h->md.ngp;
+    if (with_gp) {
+        if (!h->P.use_gp) return fail(GPMPC_ERR_STATE, "with_gp = 1 while the handle's GPs are off (gpmpc_use_gp)");
+        for (int g = 0; g < ngp; ++g)
+            if (!h->gp[g].set) return fail(GPMPC_ERR_STATE, "GP " + std::to_string(g) + " not set");
+    }
+    const bool want_var = xi_dev || var_dev;
+    if (want_var)
+        for (int g = 0; g < ngp; ++g) {
+            if (!h->gp[g].set) return fail(GPMPC_ERR_STATE, "the variance needs GP " + std::to_string(g) + ", which is not set");
+            if (!h->gp[g].linvT) return fail(GPMPC_ERR_STATE, "the variance needs Linv (GP " + std::to_string(g) + " has none)");
+        }
+    (void)hipSetDevice(h->device);
+    // on the handle's side stream, behind the handle's last call, and drained before the call returns (gpmpc_rollout)
+    HIPCHK(ensure_side(h));
+    hipStream_t s = h->side;
+    HIPCHK(order_after_last(h, s));
+    StreamMark mark{h, s};
+    RolloutSampleArgs a{};
+    for (int i = 0; i < kMaxParams; ++i) a.r.params[i] = h->P.params[i];
+    a.r.dt = h->P.dt;
+    a.r.P = P;
+    a.r.T = T;
+    a.r.x0 = x0_dev;
+    a.r.u = u_dev;
+    a.r.x = x_dev;
+    if (with_gp)
+        for (int g = 0; g < ngp; ++g) a.r.gp[g] = h->P.gp[g];
+    a.xref = xref_dev;
+    a.xi = xi_dev;
+    a.uapp = uapp_dev;
+    a.var = var_dev;
+    a.closed = K ? 1 : 0;
+    a.clip = clip;
+    if (K)
+        for (int i = 0; i < nu * nx; ++i) a.K[i] = K[i];
+    for (int c = 0; c < nu; ++c) {
+        a.u_lo[c] = h->P.u_lo[c];
+        a.u_hi[c] = h->P.u_hi[c];
+    }
+    if (want_var)   // the exact rows and their factor, as gpmpc_gp_predict reads them (no LOVE root, no FITC overlay)
+        for (int g = 0; g < ngp; ++g) {
+            const GPDev& d = h->P.gp[g];
+            a.noise[g] = with_noise ? d.sn2 : 0.0;
+            a.vg[g] = RolloutSampleGP{d.vrows, d.linvT, d.nv, h->gp[g].npad, d.inv_ell2, d.sf2};
+        }
+    HIPCHK(launch_rollout_sample(h->model, a, with_gp != 0, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return GPMPC_OK;
+}
+
 }  // extern "C"

@@ -50,20 +50,6 @@ __device__ __forceinline__ void load_point(const PostArgs& a, int p, double (&z)
 constexpr int kPostWaves = 8;
 constexpr int kMaxCT = 16;
 
-__device__ __forceinline__ double dpp_row_sum(double v) {
-    auto mv = [](double x, auto ctrl) {
-        const long long b = __double_as_longlong(x);
-        const int lo = __builtin_amdgcn_update_dpp(0, (int)b, decltype(ctrl)::value, 0xf, 0xf, false);
-        const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), decltype(ctrl)::value, 0xf, 0xf, false);
-        return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-    };
-    v += mv(v, std::integral_constant<int, 0x128>{});   // row_ror:8
-    v += mv(v, std::integral_constant<int, 0x124>{});   // row_ror:4
-    v += mv(v, std::integral_constant<int, 0x4E>{});    // quad_perm [2,3,0,1]
-    v += mv(v, std::integral_constant<int, 0xB1>{});    // quad_perm [1,0,3,2]
-    return v;
-}
-
 // sum over the four lanes of a DPP quad (lanes 4i .. 4i + 3), left in each of them
 __device__ __forceinline__ double dpp_quad_sum(double v) {
     auto mv = [](double x, auto ctrl) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
 
 namespace gpmpc {
 
@@ -256,6 +257,22 @@ __device__ __forceinline__ void exp_rbf_n(double (&x)[K]) {
 #pragma unroll
     for (int k = 0; k < K; ++k)
         x[k] = __hiloint2double(__double2hiint(p[k]) + (__double2loint(t[k]) << 20), __double2loint(p[k]));
+}
+
+// sum over the 16 lanes of a DPP row (lanes 16i .. 16i + 15), left in each of them (the variance kernels of
+// gp_kernels.hip and sqp_kernel.hip rollout_sample_kernel: the squared norms over the column lanes)
+__device__ __forceinline__ double dpp_row_sum(double v) {
+    auto mv = [](double x, auto ctrl) {
+        const long long b = __double_as_longlong(x);
+        const int lo = __builtin_amdgcn_update_dpp(0, (int)b, decltype(ctrl)::value, 0xf, 0xf, false);
+        const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), decltype(ctrl)::value, 0xf, 0xf, false);
+        return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+    };
+    v += mv(v, std::integral_constant<int, 0x128>{});   // row_ror:8
+    v += mv(v, std::integral_constant<int, 0x124>{});   // row_ror:4
+    v += mv(v, std::integral_constant<int, 0x4E>{});    // quad_perm [2,3,0,1]
+    v += mv(v, std::integral_constant<int, 0xB1>{});    // quad_perm [1,0,3,2]
+    return v;
 }
 
 // Up to kMaxGP posterior evaluations in one launch (grid.y = GP).
@@ -647,6 +664,29 @@ struct RolloutLinArgs {
     double* B;
 };
 hipError_t launch_rollout_lin(int model, const RolloutLinArgs& a, bool with_gp, hipStream_t stream);
+// A closed-loop sample of the rollout (sqp_kernel.hip rollout_sample_kernel; gpmpc_rollout_sample fills it), by value:
+// per step the applied input u_k = clip(u_nom,k + K (x_k - xref_k)), every GP's exact variance at z_k[gp_src_g] with
+// that input, one draw e_g = sqrt(max(var_g + noise_g, 0)) xi_g of its residual, and rollout_kernel's RK4 step with
+// mean_g + e_g in place of the mean at every substage.
+struct RolloutSampleGP {         // what the variance reads of GPDev (the exact rows and their factor)
+    const double* vrows;         // [nv][4]
+    const double* linvT;         // [npad][npad]
+    int32_t nv, npad;
+    double inv_ell2, sf2;
+};
+struct RolloutSampleArgs {
+    RolloutArgs r;               // r.u: the nominal inputs
+    const double* xref;          // [P][T+1][nx], read when closed
+    const double* xi;            // [P][T][n_gp] standard-normal draws, or null (no disturbance)
+    double* uapp;                // [P][T][nu] the applied inputs, or null
+    double* var;                 // [P][T][n_gp], or null
+    int32_t closed, clip;
+    double K[kMaxNU * kMaxNX];   // [nu][nx] row-major
+    double u_lo[kMaxNU], u_hi[kMaxNU];
+    double noise[kMaxGP];        // with_noise * sn2_g
+    RolloutSampleGP vg[kMaxGP];  // read when xi or var is given
+};
+hipError_t launch_rollout_sample(int model, const RolloutSampleArgs& a, bool with_gp, hipStream_t stream);
 // The state covariance along a finished rollout (rollout_cov.hip; gpmpc_rollout_lin fills it), by value:
 //   S_0 = cov0 or zero,  S_{k+1} = Phi_k S_k Phi_k^T + Bd diag(q_k) Bd^T,  Phi_k = A_k + B_k K (A_k: open loop),
 //   q_k[j] = dt^2 sum_g W_{j,g}(x_k, u_k) (var[p][k][g] + noise[g])     (Model::var_weights, Bd = Model::unc)

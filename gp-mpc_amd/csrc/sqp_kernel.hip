@@ -4273,6 +4273,227 @@ hipError_t launch_rollout_lin(int model, const RolloutLinArgs& a, bool with_gp, 
     return hipErrorInvalidValue;
 }
 
+// Exact posterior variances of one GP at the wave's 16 points, inside the step loop of rollout_sample_kernel:
+// vs[point] = sf2 - |L^-1 k(X, z_point)|^2, the inner product of gp_var_tri_kernel / gp_post_kernel on
+// v_mfma_f64_16x16x4_f64.  Lane (kq, lc) = (lane >> 4, lane & 15) holds z of point lc; per K-step of four training
+// rows its A operand is k(x_{4s + kq}, z_lc) and its B operand (L^-1)^T[4s + kq][16 t + lc], so acc[t][r] =
+// V[point kq + 4r][column 16 t + lc].  The column tiles (npad / 16, a run-time value) are taken in groups of at most
+// kSampleCT accumulators, the kernel values regenerated per group; the zero triangle (rows below a tile's columns) is
+// skipped.  The wave works alone, so there is nobody to share a staged panel with and every B entry is used by
+// exactly one MFMA: the fragments come straight from global memory / L2 (no LDS round trip), a whole panel's
+// (16 rows x the group's tiles) issued before its first MFMA, through buffer loads on a resource of the panel's 16
+// rows, which return zero past it and keep their place ahead of the per-tile branches.
+constexpr int kSampleCT = 16;
+__device__ __forceinline__ void sample_var_tiles(const RolloutSampleGP& g, const double (&z)[3], double* vs, int lane) {
+    const int lc = lane & 15, kq = lane >> 4;
+    const double c = -0.5 * g.inv_ell2, sf2 = g.sf2;
+    const int npad = g.npad, ntile = npad / 16, nv = g.nv;
+    const double4* rows = reinterpret_cast<const double4*>(g.vrows);
+    double sq[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int t0 = 0; t0 < ntile; t0 += kSampleCT) {
+        const int tn = min(kSampleCT, ntile - t0);
+        const int npan = t0 + tn;   // K rows < 16 (t0 + tn): the upper triangle
+        f64x4 acc[kSampleCT];
+#pragma unroll
+        for (int t = 0; t < kSampleCT; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+        for (int pan = 0; pan < npan; ++pan) {
+            const int lt0 = max(pan - t0, 0);
+            const __amdgpu_buffer_rsrc_t rb = make_rsrc(g.linvT + (size_t)16 * pan * npad, 16 * npad * 8);
+            double bv[4][kSampleCT];
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const int off = ((4 * ks + kq) * npad + 16 * t0 + lc) * 8;
+#pragma unroll
+                for (int t = 0; t < kSampleCT; ++t)
+                    bv[ks][t] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rb, off + 128 * t, 0, 0));
+            }
+            double kv[4];   // the panel's four kernel values: independent exps
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const double4 r = rows[max(min(16 * pan + 4 * ks + kq, nv - 1), 0)];
+                const double d0 = r.x - z[0], d1 = r.y - z[1], d2 = r.z - z[2];
+                kv[ks] = c * fma(d0, d0, fma(d1, d1, d2 * d2));
+            }
+            exp_rbf_n<4>(kv);
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) kv[ks] = (16 * pan + 4 * ks + kq < nv) ? sf2 * kv[ks] : 0.0;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int t = 0; t < kSampleCT; ++t)
+                    if (t >= lt0 && t < tn) acc[t] = mfma64(kv[ks], bv[ks][t], acc[t]);
+        }
+#pragma unroll
+        for (int t = 0; t < kSampleCT; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sq[r] = (t < tn) ? fma(acc[t][r], acc[t][r], sq[r]) : sq[r];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sq[r] = dpp_row_sum(sq[r]);   // over the 16 column lanes
+    if (lc == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) vs[kq + 4 * r] = sf2 - sq[r];
+    }
+}
+
+// A closed-loop sample of the learned model over T steps (gpmpc_rollout_sample), the steps in sequence inside one
+// launch, in the layout of rollout_kernel<ID, true> for every variant: one wavefront per 16 trajectories, lane l on
+// trajectory l & 15, the four 16-lane rows redundant but for the tile sums; lanes 0..15 touch memory.  Per step:
+//   the applied input  u_k[c] = u_nom,k[c] + sum_j K[c][j] (x_k[j] - xref_k[j]) as an fma chain over ascending j, then
+//                      clipped to [u_lo, u_hi] by comparisons that leave a NaN a NaN;
+//   MODE >= kSampleVar the variances of every GP at z_k[gp_src_g] with that input (sample_var_tiles), handed from the
+//                      lane that owns a point's sum to the lanes of its trajectory through NGP x 16 doubles of LDS;
+//   MODE == kSampleDraw  e_g = sqrt(max(var_g + noise_g, 0)) xi_k[g], held over the step;
+//   the state          rollout_kernel's RK4 step, statement for statement, with gm[g] = mean_g + e_g at every substage
+//                      (a control-only GP evaluated at substage 0 alone; GP = false: the means are zero).
+// Below kSampleDraw the draw is not in the arithmetic at all, so with K and the clip off the states are
+// rollout_kernel's bits (GP = false: plant_step_kernel's, the means the constant zero as in rollout_lin_kernel).
+enum : int { kSamplePlain = 0, kSampleVar = 1, kSampleDraw = 2 };
+template <int ID, bool GP, int MODE>
+__global__ __launch_bounds__(64) void rollout_sample_kernel(RolloutSampleArgs b) {
+    using M = Model<ID>;
+    constexpr int NX = M::NX, NU = M::NU, NGP = M::NGP;
+    const RolloutArgs& a = b.r;
+    __shared__ double zb[GP ? NGP * 16 * 4 : 1], czz[GP ? NGP * 16 : 1], out[GP ? NGP * 16 * 4 : 1];
+    __shared__ double vs[MODE >= kSampleVar ? NGP * 16 : 1];
+    const int lane = threadIdx.x;
+    const int p = blockIdx.x * 16 + (lane & 15);
+    const bool store = p < a.P && lane < 16;
+    const size_t tr = (size_t)min(p, a.P - 1);
+    const double* u = a.u + tr * a.T * NU;
+    const double* xr = b.xref + tr * (a.T + 1) * NX;
+    const double* xi_p = b.xi + tr * a.T * NGP;
+    double* x = a.x + tr * (a.T + 1) * NX;
+    double* uo = b.uapp + tr * a.T * NU;
+    double* vo = b.var + tr * a.T * NGP;
+    double pv[kMaxParams];
+#pragma unroll
+    for (int i = 0; i < kMaxParams; ++i) pv[i] = a.params[i];
+    const double dt = a.dt;
+    double xs[NX], us[NU], k[NX], acc[NX], xi[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xs[i] = a.x0[tr * NX + i];
+    if (store) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) x[i] = xs[i];
+    }
+    const double cs[4] = {0.0, 0.5, 0.5, 1.0}, ws[4] = {1.0, 2.0, 2.0, 1.0};
+    for (int step = 0; step < a.T; ++step) {
+#pragma unroll
+        for (int c = 0; c < NU; ++c) {
+            double v = u[(size_t)step * NU + c];
+            if (b.closed) {
+#pragma unroll
+                for (int j = 0; j < NX; ++j) v = fma(b.K[c * NX + j], xs[j] - xr[(size_t)step * NX + j], v);
+            }
+            if (b.clip) v = v < b.u_lo[c] ? b.u_lo[c] : (v > b.u_hi[c] ? b.u_hi[c] : v);
+            us[c] = v;
+        }
+        if (store && b.uapp != nullptr) {
+#pragma unroll
+            for (int c = 0; c < NU; ++c) uo[(size_t)step * NU + c] = us[c];
+        }
+        double e[NGP];
+#pragma unroll
+        for (int g = 0; g < NGP; ++g) e[g] = 0.0;
+        if constexpr (MODE >= kSampleVar) {
+            static_for<NGP>([&](auto gi) {
+                constexpr int G = decltype(gi)::value;
+                double z[3];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    const int src = M::gp_src[G][d];
+                    z[d] = d < M::gp_dim[G] ? (src < NX ? xs[src] : us[src - NX]) : 0.0;
+                }
+                sample_var_tiles(b.vg[G], z, vs + G * 16, lane);
+            });
+            __syncthreads();
+#pragma unroll
+            for (int g = 0; g < NGP; ++g) {
+                const double v = vs[g * 16 + (lane & 15)];
+                if (store && b.var != nullptr) vo[(size_t)step * NGP + g] = v;
+                if constexpr (MODE == kSampleDraw) e[g] = sqrt(fmax(v + b.noise[g], 0.0)) * xi_p[(size_t)step * NGP + g];
+            }
+            __syncthreads();   // (the next step's sums are written behind these reads)
+        }
+        double gm[kMaxGP] = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (!GP && MODE == kSampleDraw) {
+#pragma unroll
+            for (int g = 0; g < NGP; ++g) gm[g] = e[g];
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) xi[i] = (s == 0) ? xs[i] : fma(cs[s] * dt, k[i], xs[i]);
+            if constexpr (GP) {
+                static_for<NGP>([&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    if (s > 0 && !M::gp_state_dep[G]) return;
+                    const GPDev& g = a.gp[G];
+                    double zc[3];
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        const int src = M::gp_src[G][d];
+                        zc[d] = d < M::gp_dim[G] ? (src < NX ? xi[src] : us[src - NX]) - g.xbar[d] : 0.0;
+                    }
+                    if (lane < 16) {
+                        double* dst = zb + (G * 16 + lane) * 4;
+                        dst[0] = zc[0];
+                        dst[1] = zc[1];
+                        dst[2] = zc[2];
+                        dst[3] = 1.0;
+                        czz[G * 16 + lane] = -0.5 * g.inv_ell2 * fma(zc[0], zc[0], fma(zc[1], zc[1], zc[2] * zc[2]));
+                    }
+                });
+                __syncthreads();
+                static_for<NGP>([&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    if (s > 0 && !M::gp_state_dep[G]) return;
+                    const GPDev& g = a.gp[G];
+                    gp_tiles_dispatch(g.tX, g.tW, g.ntile, zb + G * 64, czz + G * 16, out + G * 64, lane, 1);
+                });
+                __syncthreads();
+                static_for<NGP>([&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    if (s > 0 && !M::gp_state_dep[G]) return;
+                    gm[G] = a.gp[G].sf2 * out[(G * 16 + (lane & 15)) * 4];
+                    if constexpr (MODE == kSampleDraw) gm[G] += e[G];
+                });
+            }
+            M::f(pv, xi, us, gm, k);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) acc[i] = (s == 0) ? k[i] : fma(ws[s], k[i], acc[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < NX; ++i) xs[i] = fma(dt / 6.0, acc[i], xs[i]);
+        if (store) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) x[(size_t)(step + 1) * NX + i] = xs[i];
+        }
+    }
+}
+
+template <int ID, bool GP>
+static hipError_t launch_rollout_sample_of(const RolloutSampleArgs& a, hipStream_t stream) {
+    const dim3 grid((a.r.P + 15) / 16), block(64);
+    if (a.xi != nullptr)
+        hipLaunchKernelGGL((rollout_sample_kernel<ID, GP, kSampleDraw>), grid, block, 0, stream, a);
+    else if (a.var != nullptr)
+        hipLaunchKernelGGL((rollout_sample_kernel<ID, GP, kSampleVar>), grid, block, 0, stream, a);
+    else
+        hipLaunchKernelGGL((rollout_sample_kernel<ID, GP, kSamplePlain>), grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_rollout_sample(int model, const RolloutSampleArgs& a, bool with_gp, hipStream_t stream) {
+    switch (model) {
+        case kQuad2D: return with_gp ? launch_rollout_sample_of<kQuad2D, true>(a, stream) : launch_rollout_sample_of<kQuad2D, false>(a, stream);
+        case kQuad3D: return with_gp ? launch_rollout_sample_of<kQuad3D, true>(a, stream) : launch_rollout_sample_of<kQuad3D, false>(a, stream);
+        case kCartpole: return with_gp ? launch_rollout_sample_of<kCartpole, true>(a, stream) : launch_rollout_sample_of<kCartpole, false>(a, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
 // LINEAR_LS stage costs of the stored solution (gpmpc_set_cost_buffer), one thread per (instance,
 // stage), queued right behind the SQP launch: cost[b][k] = 1/2 ||y_k - y_ref,k||^2_W, y = [x; u],
 // W = dt blkdiag(Q, R) on stages 0..H-1 and Q on stage H (gpmpc.py:231-239, mpc.py:101-102, acados

@@ -65,6 +65,7 @@ SIGNATURES = {
     "gpmpc_plant_step": (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout": (_I, [_P, _I, _I, _P, _P, _I, _P, _P]),
     "gpmpc_rollout_lin": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "gpmpc_rollout_sample": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
     "gpmpc_preprocess": (_I, [_P, _I, _P, _P, _P, _I, _P, _D, _D, _P, _P, _P]),
     "gpmpc_gp_informative": (_I, [_P, _I, _P, _P, _I, _P, _P, _P]),
     "gpmpc_gp_select": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),

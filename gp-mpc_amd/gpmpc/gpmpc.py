@@ -650,6 +650,51 @@ class GPMPC:
         return predict_trajectory(self.solver, x0, u, with_gp=with_gp, return_var=return_var, return_cov=True,
                                   feedback=K, with_noise=with_noise)
 
+    def sample_trajectories(self, x0, u, n_samples: int, seed: int = 0, feedback=None, clip: bool = True,
+                            with_noise: bool = True, with_gp: bool = True):
+        """Futures drawn from what the GPs believe (``BatchSolver.rollout_sample``): every input trajectory is
+        repeated ``n_samples`` times and each copy rolled out with its own draws of the GPs' residuals, one per GP
+        and step, at the posterior variance of the point it has reached (plus the likelihood noise with
+        ``with_noise``).  numpy in and out: one trajectory, ``x0`` (nx,) and ``u`` (T, nu), gives ``x``
+        (n_samples, T+1, nx) and the applied inputs (n_samples, T, nu); a batch, (P, nx) and (P, T, nu), gives
+        (P, n_samples, T+1, nx) and (P, n_samples, T, nu).  ``feedback`` is None (the inputs are applied as given),
+        ``"lqr"`` (the controller's ``lqr_gain``) or a gain (nu, nx): the applied input is then
+        ``u_k + K (x_k - xbar_k)`` around the mean prediction ``xbar = predict_trajectory(x0, u)``, clipped to the
+        input box with ``clip``.  The draws are ``torch.randn`` on the device from a generator seeded with ``seed``:
+        equal seeds give equal samples.  The GPs must be uploaded (``reset()`` after ``train_gp``)."""
+        assert not getattr(self, "_requires_recompile", False), "GP model must be uploaded (call reset())"
+        K = self.lqr_gain if isinstance(feedback, str) and feedback == "lqr" else feedback
+        if isinstance(K, str):
+            raise ValueError('feedback is None, "lqr" or a gain (nu, nx)')
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError("n_samples must be at least 1")
+        x0 = np.asarray(x0, dtype=np.float64)
+        u = np.asarray(u, dtype=np.float64)
+        single = x0.ndim == 1
+        if single:
+            if u.ndim != 2:
+                raise ValueError("one trajectory takes x0 (nx,) and u (T, nu)")
+            x0, u = x0[None], u[None]
+        elif x0.ndim != 2 or u.ndim != 3 or u.shape[0] != x0.shape[0]:
+            raise ValueError("a batch takes x0 (P, nx) and u (P, T, nu)")
+        solver = self.solver
+        dev = solver.device
+        P, T = u.shape[:2]
+        x0t = torch.as_tensor(np.ascontiguousarray(x0), device=dev).repeat_interleave(n_samples, dim=0)
+        ut = torch.as_tensor(np.ascontiguousarray(u), device=dev).repeat_interleave(n_samples, dim=0)
+        xref = None
+        if K is not None:
+            xbar = predict_trajectory(solver, x0, u, with_gp=with_gp)
+            xref = torch.as_tensor(np.ascontiguousarray(xbar), device=dev).repeat_interleave(n_samples, dim=0)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        xi = torch.randn(P * n_samples, T, self.model.n_gp, dtype=torch.float64, device=dev, generator=gen)
+        out = solver.rollout_sample(x0t, ut, xref=xref, K=K, clip=clip, xi=xi, with_gp=with_gp, with_noise=with_noise)
+        x = out["x"].cpu().numpy().reshape(P, n_samples, T + 1, -1)
+        ua = out["u"].cpu().numpy().reshape(P, n_samples, T, -1)
+        return (x[0], ua[0]) if single else (x, ua)
+
     def reference_trajectory(self) -> np.ndarray:
         """`gpmpc/gpmpc.py:509-514`."""
         indices = np.arange(self.traj_step, self.traj_step + self.T + 1) % self.traj.shape[-1]

@@ -260,6 +260,30 @@ def prediction_calibration(ctrl, data: dict, horizon: int, stride: int = 1, feed
     return np.sqrt(z2.mean(axis=0))
 
 
+def tightening_coverage(ctrl, x0, u, n_samples: int, seed: int = 0, feedback="lqr", with_noise: bool = True) -> np.ndarray:
+    """Whether the linearised, diagonal covariance the tightening relies on covers what the model's own belief
+    produces.  ``x0`` (nx,) / (P, nx) and ``u`` (T, nu) / (P, T, nu) as in ``ctrl.predict_trajectory``; ``x̄`` and
+    ``cov`` come from ``ctrl.predict_trajectory(x0, u, return_cov=True, feedback=feedback, with_noise=with_noise)`` and
+    the particles from ``ctrl.sample_trajectories(x0, u, n_samples, seed=seed, feedback=feedback,
+    with_noise=with_noise)``, the same feedback and noise.  Returns (T+1, nx): for stage k and state i the fraction
+    of particles (over samples and trajectories) with ``|x_k[i] - x̄_k[i]| <= icdf sqrt(cov_k[i][i])``, ``icdf`` the
+    controller's ``inverse_cdf``.  Stage 0 and entries whose predicted variance is zero somewhere report NaN.  A value
+    near the controller's ``prob`` means the tightening's half-width holds the sampled futures as often as it claims."""
+    xbar, cov = ctrl.predict_trajectory(x0, u, return_cov=True, feedback=feedback, with_noise=with_noise)
+    x, _ = ctrl.sample_trajectories(x0, u, n_samples, seed=seed, feedback=feedback, with_noise=with_noise)
+    xbar, cov, x = np.asarray(xbar), np.asarray(cov), np.asarray(x)
+    if xbar.ndim == 2:
+        xbar, cov, x = xbar[None], cov[None], x[None]
+    var = np.diagonal(cov, axis1=-2, axis2=-1)                                   # (P, T+1, nx)
+    with np.errstate(invalid="ignore"):
+        half = ctrl.inverse_cdf * np.sqrt(var)
+    inside = np.abs(x - xbar[:, None]) <= half[:, None]                          # (P, S, T+1, nx)
+    frac = inside.mean(axis=(0, 1))
+    frac[~(var > 0.0).all(axis=0)] = np.nan
+    frac[0] = np.nan
+    return frac
+
+
 def learn(n_epochs: int, ctrl, lr: float, gp_iterations: int, seed: int, samples_per_epoch: int,
           episode_len: int, x0: np.ndarray | None = None, tstep0: np.ndarray | None = None,
           report_prediction: int = 0):

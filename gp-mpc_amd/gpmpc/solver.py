@@ -793,3 +793,51 @@ class BatchSolver:
                                               _lib.ptr(out.get("var")), None if K is None else K.ctypes.data,
                                               _lib.ptr(cov0), int(bool(with_noise)), _lib.ptr(out.get("cov"))))
         return out
+
+    def rollout_sample(self, x0: torch.Tensor, u: torch.Tensor, xref: torch.Tensor | None = None, K=None,
+                       clip: bool = False, xi: torch.Tensor | None = None, with_gp: bool = True,
+                       with_noise: bool = False, var: bool = False) -> dict:
+        """One closed-loop sample per trajectory of the future the learned model believes in
+        (gpmpc_rollout_sample): :meth:`rollout` with the input recomputed at every step,
+        ``u_k = u[:, k] + K (x_k - xref[:, k])`` (``K`` (nu, nx), host, with ``xref`` (P, T+1, nx); both None: no
+        feedback), clipped to the model's input box with ``clip=True``, and one draw of every GP's residual,
+        ``sqrt(max(var_g + noise_g, 0)) xi[:, k, g]``, added to its mean at every RK4 substage of the step (``xi``
+        (P, T, n_gp): the caller's standard-normal draws, None for no disturbance; the variance is the exact
+        posterior variance at ``(x_k, u_k)`` with the applied input, plus the likelihood noise with
+        ``with_noise=True``).  Returns a dict: ``x`` (P, T+1, nx), ``u`` (P, T, nu) the applied inputs and, with
+        ``var=True``, ``var`` (P, T, n_gp) without likelihood noise.  With no ``xi``, no ``K`` and no clip ``x`` is
+        :meth:`rollout`'s bits.  The disturbance and the variance need every GP set with its Linv.  Synchronises
+        the current stream first, as :meth:`rollout` does, and returns with its work completed."""
+        x0 = x0.to(self.device, torch.float64).contiguous()
+        u = u.to(self.device, torch.float64).contiguous()
+        if x0.ndim != 2 or x0.shape[1] != self.nx:
+            raise ValueError(f"x0 must be (P, nx={self.nx})")
+        if u.ndim != 3 or u.shape[0] != x0.shape[0] or u.shape[2] != self.nu:
+            raise ValueError(f"u must be (P={x0.shape[0]}, T, nu={self.nu})")
+        P, T = int(u.shape[0]), int(u.shape[1])
+        if (K is None) != (xref is None):
+            raise ValueError("K and xref go together (both given, or both None)")
+        if K is not None:
+            K = _c(K)
+            if K.shape != (self.nu, self.nx):
+                raise ValueError(f"K must be (nu={self.nu}, nx={self.nx})")
+            xref = xref.to(self.device, torch.float64).contiguous()
+            if tuple(xref.shape) != (P, T + 1, self.nx):
+                raise ValueError(f"xref must be (P={P}, T+1={T + 1}, nx={self.nx})")
+        if xi is not None:
+            xi = xi.to(self.device, torch.float64).contiguous()
+            if tuple(xi.shape) != (P, T, self.spec.n_gp):
+                raise ValueError(f"xi must be (P={P}, T={T}, n_gp={self.spec.n_gp})")
+
+        def new(*shape):
+            return torch.empty(*shape, dtype=torch.float64, device=self.device)
+
+        out = {"x": new(P, T + 1, self.nx), "u": new(P, T, self.nu)}
+        if var:
+            out["var"] = new(P, T, self.spec.n_gp)
+        torch.cuda.current_stream(self.device).synchronize()
+        _lib.check(self.lib.gpmpc_rollout_sample(self._h, P, T, x0.data_ptr(), u.data_ptr(), _lib.ptr(xref),
+                                                 None if K is None else K.ctypes.data, int(bool(clip)), _lib.ptr(xi),
+                                                 int(bool(with_gp)), int(bool(with_noise)), out["x"].data_ptr(),
+                                                 out["u"].data_ptr(), _lib.ptr(out.get("var"))))
+        return out

@@ -29,6 +29,8 @@
  * returns.  Unlike gpmpc_gp_inducing it has device inputs of the caller's, and they are the caller's to order:
  * x0_dev and u_dev must be complete when the call is made; the outputs are complete when it returns.
  * gpmpc_rollout_lin follows the same rule as gpmpc_rollout in every respect (cov0_dev is one more input of the caller's).
+ * gpmpc_rollout_sample does too: xref_dev and xi_dev are further inputs of the caller's, complete when the call is
+ * made, and K is read on the host before the call returns.
  * The library reads no environment variables: every option is an explicit call.
  */
 #ifndef GPMPC_MI355X_H
@@ -503,6 +505,45 @@ gpmpc_status gpmpc_rollout(gpmpc_handle* h, int32_t P, int32_t T, const double* 
 gpmpc_status gpmpc_rollout_lin(gpmpc_handle* h, int32_t P, int32_t T, const double* x0_dev, const double* u_dev,
                                int32_t with_gp, double* x_dev, double* A_dev, double* B_dev, double* var_dev,
                                const double* K, const double* cov0_dev, int32_t with_noise, double* cov_dev);
+
+/* One closed-loop sample per trajectory of the future the learned model believes in: gpmpc_rollout with the input
+ * recomputed from a feedback law at every step and a draw of every GP's residual added to its mean, one launch for
+ * the whole horizon (csrc/sqp_kernel.hip rollout_sample_kernel).  P, T, x0_dev, with_gp and x_dev are gpmpc_rollout's;
+ * u_dev [P][T][nu] holds the NOMINAL inputs.  For step k = 0 .. T-1 of a trajectory:
+ *   applied input  v_c = u_nom,k[c], then for j ascending v_c = fma(K[c][j], x_k[j] - xref_k[j], v_c); with clip = 1
+ *                  u_k[c] = v_c < u_lo[c] ? u_lo[c] : (v_c > u_hi[c] ? u_hi[c] : v_c) with gpmpc_set_model's input box
+ *                  (a NaN stays a NaN), else u_k[c] = v_c.  K is a HOST array [nu][nx], row-major, read before the
+ *                  call returns (it travels by value), or NULL for no feedback; xref_dev [P][T+1][nx] is the feedback
+ *                  reference, row k read at step k (row T is not read), NULL if and only if K is NULL.
+ *   variance       var_{g,k}: the exact posterior variance of GP g without likelihood noise at z_k[gp_src_g],
+ *                  z_k = [x_k; u_k] with the APPLIED input: the quantity gpmpc_gp_predict(with_noise = 0) computes (inert
+ *                  rows inert, a LOVE root ignored, a FITC overlay not changing it), evaluated inside the step loop
+ *                  and only when xi_dev or var_dev is given.  The sums run in another order than that call's, so the
+ *                  two agree to rounding, not bit for bit.
+ *   disturbance    e_g = sqrt(fmax(var_{g,k} + with_noise noise_g, 0)) xi[k][g]: one draw of GP g's residual, held
+ *                  over the step.  xi_dev [P][T][n_gp] holds the caller's standard-normal draws (the library draws
+ *                  none), NULL for no disturbance.
+ *   state          x_{k+1}: gpmpc_rollout's RK4 step with mean_g(z at the substage) + e_g in place of the mean at every
+ *                  substage (a control-only GP is evaluated at substage 0 alone; with_gp = 0: the means are zero and
+ *                  the value is e_g).  The draw so passes through the model's own df/dgm, with its sign and its
+ *                  correlation across state rows; the diagonal dt^2 W (var + noise) of gpmpc_rollout_lin's cov_dev and
+ *                  of the tightening is its first-order marginal.
+ * x_dev [P][T+1][nx] receives the states, uapp_dev [P][T][nu] (may be NULL) the applied inputs, var_dev [P][T][n_gp]
+ * (may be NULL) the variances.
+ * With xi_dev = NULL, K = NULL and clip = 0, x_dev receives gpmpc_rollout's bits: the draw is then not in the
+ * arithmetic at all (it is not multiplied by zero).  A trajectory's outputs depend on its own inputs and the handle
+ * only, whatever P is and wherever it sits in the batch; the first k+1 rows of a T-step call are those of a k-step
+ * call; a non-finite input poisons its own trajectory only; every sum has a fixed order, there are no atomics, and
+ * nothing is refused on the device.
+ * THE CALL IS SYNCHRONOUS and takes no stream (see "Streams" above).  It needs no scratch and allocates nothing.
+ * Refused with nothing written: everything gpmpc_rollout refuses of P, T, x0_dev, u_dev, x_dev and with_gp; also
+ * with_noise or clip not 0 or 1, exactly one of K and xref_dev given, a non-finite entry of K (GPMPC_ERR_ARG); a call
+ * before gpmpc_set_model, with_gp = 1 with the GPs off or a GP unset, xi_dev or var_dev with a GP not set or set
+ * without Linv (GPMPC_ERR_STATE). */
+gpmpc_status gpmpc_rollout_sample(gpmpc_handle* h, int32_t P, int32_t T, const double* x0_dev, const double* u_dev,
+                                  const double* xref_dev, const double* K, int32_t clip, const double* xi_dev,
+                                  int32_t with_gp, int32_t with_noise, double* x_dev, double* uapp_dev,
+                                  double* var_dev);
 
 /* GP training rows from transitions, on the device: GPMPC.preprocess_data of the build (the reference's
  * gpmpc/gpmpc.py:113-151) for the handle's model, csrc/gp_observe.hip.  x_dev [P][nx], u_dev [P][nu] and

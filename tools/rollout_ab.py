@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Timing of BatchSolver.rollout (gpmpc_rollout) beside the chain of plant steps, and of BatchSolver.rollout_lin
-(gpmpc_rollout_lin) beside the plain rollout.
+"""Timing of BatchSolver.rollout (gpmpc_rollout) beside the chain of plant steps, of BatchSolver.rollout_lin
+(gpmpc_rollout_lin) beside the plain rollout, and of BatchSolver.rollout_sample (gpmpc_rollout_sample) beside the
+step-by-step host loop it replaces.
 
 Times, between two device synchronisations, one call of each side on the same inputs (x0 from initial_states, u near
 u_eq):
@@ -15,6 +16,14 @@ u_eq):
     lin_var    rollout_lin(var=True)               plus the gather and the variance launches
     lin_cov    rollout_lin(cov=True, K=lqr, with_noise=True)   plus the covariance launch (variances in scratch)
     lin_prior  rollout_lin(with_gp=False)          the prior's Jacobians
+    sample     rollout_sample(xref=rollout, K=lqr, clip=True, xi=randn, with_noise=True, var=True)   one launch
+    sample_host  what could be done for the same end before: T times {feedback and clip in torch, rollout(T=1,
+               var=True), the draw sqrt(var + noise) xi in torch, added to the new state through dt df/dgm at the
+               equilibrium}: three launches, a drain and the torch glue per step (a first-order stand-in for the
+               draw, which the library could not pass through the RK4 substages)
+
+`--coverage S` instead prints learning.tightening_coverage of one controller of the model (GPs fitted on `--train`
+rows, horizon `--steps`, S samples of each of 8 trajectories under the LQR gain) as JSON.
 
 The sides alternate in one process: `--repeats` rounds, each timing every side `--calls` times after `--warmup`
 untimed calls; a round's figure is the median over its calls.  Prints one JSON object: per side the median round's
@@ -39,7 +48,42 @@ for p in (ROOT / "gp-mpc_amd", ROOT):
     if str(p) not in sys.path:
         sys.path.insert(0, str(p))
 
-SIDES = ("gp", "gp_var", "prior", "prior_var", "plant", "lin", "lin_var", "lin_cov", "lin_prior")
+SIDES = ("gp", "gp_var", "prior", "prior_var", "plant", "lin", "lin_var", "lin_cov", "lin_prior", "sample", "sample_host")
+
+
+def dfdgm(spec):
+    """(n_gp, nx): the state derivative's sensitivity to each GP mean at the equilibrium, from the CPU oracle's model."""
+    from oracle import gpmpc_oracle as O
+
+    sd = spec.to_dict()
+    dyn = O.Dynamics(sd, None)
+    x, u = np.zeros(spec.nx), np.asarray(spec.u_eq, dtype=np.float64)
+    gg = [np.zeros(len(idx)) for idx in sd["gp_inputs"]]
+    rows = []
+    for g in range(spec.n_gp):
+        up, dn = [0.0] * spec.n_gp, [0.0] * spec.n_gp
+        up[g], dn[g] = 0.5, -0.5
+        rows.append(dyn._f(dyn.p, dyn.g, x, u, up, gg)[0] - dyn._f(dyn.p, dyn.g, x, u, dn, gg)[0])
+    return np.array(rows)
+
+
+def coverage(args, spec):
+    from gpmpc.gpmpc import GPMPC
+    from gpmpc.learning import tightening_coverage
+    from gpmpc.synthetic import initial_states, make_training_data
+
+    data = make_training_data(spec, args.train, seed=1)
+    ctrl = GPMPC(spec.name, horizon=args.steps, batch=8, variance="exact")
+    ctrl.train_gp(np.hstack([X for X, _ in data]), np.column_stack([y for _, y in data]), lr=0.05, iterations=20)
+    ctrl.reset()
+    x0, _ = initial_states(spec, ctrl.traj, 8)
+    u = spec.u_eq + 0.1 * np.random.default_rng(args.seed).standard_normal((8, args.steps, spec.nu))
+    out = {"config": {"model": spec.name, "train": args.train, "steps": args.steps, "trajectories": 8, "n_samples": args.coverage,
+                      "seed": args.seed, "prob": ctrl.prob, "inverse_cdf": ctrl.inverse_cdf}}
+    for fb in ("lqr", None):
+        cov = tightening_coverage(ctrl, x0, u, args.coverage, seed=args.seed, feedback=fb)
+        out["lqr" if fb else "open_loop"] = [[None if np.isnan(v) else round(float(v), 4) for v in row] for row in cov]
+    print(json.dumps(out))
 
 
 def main(argv=None):
@@ -53,6 +97,7 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--seed", type=int, default=11)
     ap.add_argument("--sides", nargs="+", choices=SIDES, default=list(SIDES))
+    ap.add_argument("--coverage", type=int, default=0, metavar="S", help="print the tightening_coverage table instead")
     args = ap.parse_args(argv)
 
     import torch
@@ -66,6 +111,8 @@ def main(argv=None):
 
     spec = get_spec(args.model)
     P, T = args.trajectories, args.steps
+    if args.coverage:
+        return coverage(args, spec)
     s = BatchSolver(spec, 5, 2)
     gps = []
     for i, (X, y) in enumerate(make_training_data(spec, args.train, seed=1)):
@@ -94,6 +141,24 @@ def main(argv=None):
     side.update({"lin": lambda: s.rollout_lin(x0t, ut), "lin_var": lambda: s.rollout_lin(x0t, ut, var=True),
                  "lin_cov": lambda: s.rollout_lin(x0t, ut, cov=True, K=K, with_noise=True),
                  "lin_prior": lambda: s.rollout_lin(x0t, ut, with_gp=False)})
+    xref = s.rollout(x0t, ut)
+    xit = torch.randn(P, T, spec.n_gp, dtype=torch.float64, device=dev, generator=torch.Generator(device=dev).manual_seed(args.seed))
+    Kt = torch.tensor(K, device=dev).T.contiguous()
+    lo, hi = torch.tensor(spec.u_lo, device=dev), torch.tensor(spec.u_hi, device=dev)
+    noise = torch.tensor([DEFAULT_HYPERS[spec.name][i][2] for i in range(spec.n_gp)], dtype=torch.float64, device=dev)
+    # dt df/dgm at the equilibrium, (n_gp, nx): central differences of the prior-form model in the GP means
+    G = torch.tensor(spec.dt * dfdgm(spec), device=dev)
+
+    def sample_host():
+        x = x0t
+        for k in range(T):
+            uk = torch.minimum(torch.maximum(ut[:, k] + (x - xref[:, k]) @ Kt, lo), hi)
+            xn, var = s.rollout(x, uk[:, None].contiguous(), var=True)
+            x = xn[:, 1] + (torch.sqrt(torch.clamp(var[:, 0] + noise, min=0.0)) * xit[:, k]) @ G
+        return x
+
+    side.update({"sample": lambda: s.rollout_sample(x0t, ut, xref=xref, K=K, clip=True, xi=xit, with_noise=True, var=True),
+                 "sample_host": sample_host})
 
     def timed(fn):
         ms = []
@@ -114,6 +179,8 @@ def main(argv=None):
             rounds[name].append(timed(side[name]))
     out = {"config": {k: getattr(args, k) for k in ("model", "train", "trajectories", "steps", "calls", "warmup", "repeats",
                                                      "seed")}}
+    if "sample" in args.sides and "sample_host" in args.sides:   # how far the first-order stand-in ends from the launch
+        out["sample_vs_host_max_abs"] = float((side["sample"]()["x"][:, -1] - sample_host()).abs().max())
     for name in args.sides:
         med = statistics.median(rounds[name])
         out[name] = {"ms_per_call": round(med, 4), "ms_per_call_rounds": [round(r, 4) for r in rounds[name]],
